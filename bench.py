@@ -12,13 +12,17 @@ A "step" is one tick: one pass of the hot path (ONE launch of rgb_tick_kernel) o
 holding at most one message per server, messages already resident in HBM.  `value` counts real
 decisions only (empty NOP slots of the dense tick layout are not decisions).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what is measured or
+checked beside the headline: the oracle check of the first ticks, the replay against the generation pass, the cpu
+baseline, the host path, the WAL kernels and the literal configurations.
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL).  Groups shard by hash
 with no data-path collective (weak scaling: 65 536 groups per GPU); every 16 ticks each rank
 produces its ra_leaderboard/metrics shard and the shards are all-gathered over xGMI.
 
-The CPU oracle (oracle/) is used here ONLY as (a) the checker of the first ticks and (b) the
+The CPU oracle (oracle/) is used here ONLY, with --full, as (a) the checker of the first ticks and (b) the
 reported cpu_baseline; the timed path is the HIP library behind the C ABI.
 """
 import argparse
@@ -212,11 +216,37 @@ def run_literal(name, ticks, torch, engine, W, abi, dev, local_rank, reps=3, on_
     }
 
 
+def dump_outputs(out_dir, eng, d_dec, offset, n, max_decisions=262144, state_sample=8192):
+    """What the timed path computed in its last tick, as float64 arrays (every value is a uint32 word of the records,
+    so the conversion is exact): decisions.npy -- the tick's decisions, expanded from the compact form and ordered by
+    server (one message per server per tick), one row of 16 words per decision; state_sample.npy -- the state behind
+    the tick of a fixed, seeded sample of the servers.  Larger outputs are sampled the same way (under 64 MB in all)."""
+    from ra_amd import abi
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0x5EED)
+    dec = abi.expand_decisions(d_dec[offset:offset + n * 64].cpu().numpy().view(abi.DECISION_DTYPE))
+    dec = dec[np.argsort(dec["server"], kind="stable")]
+    if len(dec) > max_decisions:
+        dec = dec[np.sort(rng.choice(len(dec), max_decisions, replace=False))]
+    np.save(os.path.join(out_dir, "decisions.npy"), dec.view(np.uint32).reshape(len(dec), -1).astype(np.float64))
+    pick = np.sort(rng.choice(eng.n_servers, min(state_sample, eng.n_servers), replace=False))
+    st = eng.get_state()[pick]
+    np.save(os.path.join(out_dir, "state_sample.npy"), st.view(np.uint32).reshape(len(st), -1).astype(np.float64))
+    np.save(os.path.join(out_dir, "state_sample_servers.npy"), pick.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
-    ap.add_argument("--warmup", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=None, help="timed ticks (default 1000; --config4: 192)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed ticks in front of them (default 32; --config4 without --steps: 16)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the oracle check of the first ticks, the replay's "
+                         "decisions and snapshots against the generation pass, the device plan against the host's, the "
+                         "cpu baseline, the host path, the WAL kernels and the literal configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed ticks, write what the last one computed as DIR/<name>.npy (float64): its "
+                         "decisions (expanded, by server) and a fixed sample of the servers' state behind it")
     ap.add_argument("--groups", type=int, default=65536, help="Raft groups per GPU")
     ap.add_argument("--members", type=int, default=5)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0003)
@@ -229,7 +259,7 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--check-ticks", type=int, default=3,
                     help="ticks (the first of the timed window's stream, i.e. on the AGED state) compared "
-                         "bit-for-bit with the oracle before timing (rank 0)")
+                         "bit-for-bit with the oracle before timing (rank 0; --full)")
     ap.add_argument("--age", type=int, default=512,
                     help="untimed fast-forward: generator ticks applied before the warm-up/timed window, so that a "
                          "short run (--steps 20) times the long-run state (term-run tables of 2..16 runs, "
@@ -265,8 +295,21 @@ def main():
     ap.add_argument("--total-groups", type=int, default=262144, help="--config4: groups over all ranks")
     ap.add_argument("--literal-ticks", type=int, default=32,
                     help="ticks of each literal SURVEY 8(d) configuration (configs 2, 3 and 5; host-generated, every "
-                         "tick oracle-checked, then replayed and timed on the device); 0 = skip (rank 0, N=1 only)")
+                         "tick oracle-checked, then replayed and timed on the device); 0 = skip (rank 0, N=1 only; --full)")
     args = ap.parse_args()
+    c4_default = args.config4 and args.steps is None   # configs[3]: 1.3 M servers, 84 MB per tick of messages
+    if args.steps is None:
+        args.steps = 192 if c4_default else 1000
+    if args.warmup is None:
+        args.warmup = 16 if c4_default else 32
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run is the headline only: set up, warm up, time the steps
+        args.check_ticks = 0
+        args.no_cpu_baseline = args.no_host_path = True
+        args.literal_ticks = 0
+    checks = args.full and not os.environ.get("RGB_BENCH_NOCHECK")   # NOCHECK: timing probes of broken variants
 
     import torch
     import torch.distributed as dist
@@ -302,8 +345,6 @@ def main():
         SNAPSHOT_EVERY = args.snapshot_every
     use_train = args.launch == "train" and not args.generic_kernel
     G, N = args.groups, args.members
-    if args.config4 and args.steps == 1000:
-        args.steps, args.warmup = 192, 16          # 1.3 M servers: 84 MB per tick of messages, as much of decisions
     if args.config4:
         # configs[3]: a FIXED population hashed over the ranks (strong scaling); this rank's share of the global ids
         my_groups = shard.local_group_ids(args.total_groups, world, rank)
@@ -616,13 +657,13 @@ def main():
             raise SystemExit(f"TRAIN LAUNCH FAILED: flags={flags} (1 = blocks of a shard on different XCDs, 2 = a "
                              f"dependency did not commit within the spin bound); xcc of shards {xcc.tolist()}")
         # every decision of every tick of the replay against the generation pass (per-tick launches)
-        for t in range(T if not os.environ.get("RGB_BENCH_NOCHECK") else 0):   # NOCHECK: timing probes of broken variants
+        for t in range(T if checks else 0):
             nb = int(n_dec[t]) * 64
             if not torch.equal(d_dec2[t * tick_bytes:t * tick_bytes + nb], d_dec[t * tick_bytes:t * tick_bytes + nb]):
                 raise SystemExit(f"PARITY FAILURE: train decisions of tick {t} differ from the per-tick launches")
         # every leaderboard snapshot taken inside (or between) the launches against the snapshot kernel of pass 1
         snaps_checked = 0
-        if snap_in_train and not os.environ.get("RGB_BENCH_NOCHECK"):
+        if snap_in_train and checks:
             for k in range(n_bound):
                 if (k + 1) * SNAPSHOT_EVERY >= T:
                     break                                            # (the boundary behind the last tick has no reference)
@@ -632,13 +673,15 @@ def main():
                                      "differs from the snapshot kernel between per-tick launches")
                 snaps_checked += 1
         # how many decisions of a timed tick went out in the 32-byte compact form, and which kinds stayed full
-        tW = min(Wm, T - 1)
-        rawW = d_dec2[tW * tick_bytes:tW * tick_bytes + int(n_dec[tW]) * 64].cpu().numpy().view(abi.DECISION_DTYPE)
-        isc = (rawW["flags"] & abi.F_COMPACT) != 0
-        full_by_kind = np.bincount(rawW["kind"][~isc], minlength=NK)[:NK]
-        compact_info = {"fraction": round(float(isc.mean()), 4),
-                        "decision_bytes_per_tick": int(isc.sum()) * 32 + int((~isc).sum()) * 64,
-                        "full_records_by_kind": {str(k): int(v) for k, v in enumerate(full_by_kind) if v}}
+        compact_info = None
+        if args.full:
+            tW = min(Wm, T - 1)
+            rawW = d_dec2[tW * tick_bytes:tW * tick_bytes + int(n_dec[tW]) * 64].cpu().numpy().view(abi.DECISION_DTYPE)
+            isc = (rawW["flags"] & abi.F_COMPACT) != 0
+            full_by_kind = np.bincount(rawW["kind"][~isc], minlength=NK)[:NK]
+            compact_info = {"fraction": round(float(isc.mean()), 4),
+                            "decision_bytes_per_tick": int(isc.sum()) * 32 + int((~isc).sum()) * 64,
+                            "full_records_by_kind": {str(k): int(v) for k, v in enumerate(full_by_kind) if v}}
         train_info = {"ticks_per_launch": TPL, "blocks_per_tick": plan.blocks_per_tick,
                       "form": eng.train_form(),
                       "leaderboard_snapshots": ("rows of the launch (rgb_train_run_snap_device): ordered per server like one "
@@ -663,12 +706,14 @@ def main():
                                  ": nothing of the train's input preparation is outside the timed region except the "
                                  "row plan (256 bucket counts per tick)"),
                       "plan_host_ms_total": round(plan_host_ms, 3), "plan_host_us_per_tick": round(plan_host_ms * 1e3 / T, 2),
-                      "xcd_of_shard": [int(v) for v in xcc], "decisions_compared_with_per_tick_launches": int(n_dec.sum())}
+                      "xcd_of_shard": [int(v) for v in xcc], "decisions_compared_with_per_tick_launches": int(n_dec.sum()) if checks else 0}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, d_dec2 if use_train else d_dec, (T - 1) * tick_bytes, int(n_dec[T - 1]))
     checksum_pass2 = eng.state_checksum()
     # the row plan on the device (rgb_train_plan_build_device): what building the timed region's plan costs as ONE kernel
     # from the generator's bucket counts in device memory, and that its tables are the host's bit for bit (every tick)
     device_plan_info = None
-    if producer_plan and rank == 0:
+    if args.full and producer_plan and rank == 0:
         # behind the timed region: the producer's plan against the host's merge of the same counts, every tick
         buckets = d_bc.cpu().numpy().reshape(T, engine.TRAIN_BUCKETS).astype(np.uint32)
         assert np.array_equal(buckets.sum(axis=1), counts)
@@ -678,7 +723,8 @@ def main():
         if same != T:
             raise SystemExit(f"PLAN MISMATCH: the device-built plan differs from the host's in {T - same} of {T} ticks")
         train_info["device_plan"] = {"ticks_whose_tables_equal_the_host_plan": same, "ticks": T}
-    if use_train and not device_plan and not producer_plan and rank == 0 and hasattr(engine.lib(), "rgb_train_plan_build_device"):
+    if (args.full and use_train and not device_plan and not producer_plan and rank == 0
+            and hasattr(engine.lib(), "rgb_train_plan_build_device")):
         dpl = engine.TrainPlan(eng, None, snapshot_every=SNAPSHOT_EVERY if snap_in_train else 0, device_ticks=T)
         best = None
         for _ in range(5):
@@ -704,7 +750,7 @@ def main():
         if same != T:
             raise SystemExit(f"PLAN MISMATCH: the device-built plan differs from the host's in {T - same} of {T} ticks")
         train_info["device_plan"] = device_plan_info
-    assert checksum_pass2 == checksum_pass1 or os.environ.get("RGB_BENCH_NOCHECK"), "replay diverged from the generation pass"
+    assert checksum_pass2 == checksum_pass1 or not checks, "replay diverged from the generation pass"
     per_rank = None
     if use_dist:
         # every rank's own clock and its all-gathers' own time: the scaling curve can be read rank by rank

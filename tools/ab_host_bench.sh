@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; OUT=$R/gpurun_out/${1:-hb}; PRE=${2:-cs_}; RE
 for rep in $(seq 1 $REPS); do
   for v in ra_amd/csrc/variants/${PRE}*.so; do
     n=$(basename $v .so)
-    RGB_LIB=$R/$v timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --literal-ticks 0 2> $OUT/${n}_$rep.err | tail -1 > $OUT/${n}_$rep.json
+    RGB_LIB=$R/$v timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --literal-ticks 0 2> $OUT/${n}_$rep.err | tail -1 > $OUT/${n}_$rep.json
     python - $OUT/${n}_$rep.json ${n}_$rep <<'PY' | tee -a $OUT/summary.txt
 import json, sys
 try:

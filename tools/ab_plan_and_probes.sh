@@ -4,7 +4,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; OUT=$R/gpurun_out/${1:-r06e}; mkdir -p $OUT
 V=$R/ra_amd/csrc/variants
-Q="--no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
+Q="--full --no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
 one() { # name lib extra-args
   local name=$1 lib=$2; shift 2
   local nc="" ck=""; case $lib in x_*) nc=1; ck="--check-ticks 0";; esac

@@ -8,7 +8,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; TAG=${1:-r06ab}; REPS=${2:-2}; PRE=${3:-}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 V=$R/ra_amd/csrc/variants
 t0=$(date +%s); stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" | tee -a $OUT/summary.txt; }
-Q="--no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
+Q="--full --no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
 one() { # name lib extra-args
   local name=$1 lib=$2; shift 2
   local nc="" ck=""; case $lib in x_*) nc=1; ck="--check-ticks 0";; esac

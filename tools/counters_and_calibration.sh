@@ -8,7 +8,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; OUT=$R/gpurun_out/r06a; mkdir -p $OUT
 V=$R/ra_amd/csrc/variants
 t0=$(date +%s); stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" | tee -a $OUT/summary.txt; }
-Q="--no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
+Q="--full --no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
 one() { # name lib extra-args
   local name=$1 lib=$2; shift 2
   RGB_LIB=$V/$lib.so timeout 120 python bench.py $Q "$@" > $OUT/$name.json 2> $OUT/$name.err

@@ -7,7 +7,7 @@ t0=$(date +%s); stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" | tee -a $OUT/ti
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -6 | tee $OUT/gpu_suite.txt; stamp suite
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a $OUT/gpu_suite.txt; stamp smoke
 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; stamp bench_driver
-RGB_BENCH_FORCE_DIST=1 timeout 300 python bench.py --gpus 1 --steps 64 --warmup 16 --no-cpu-baseline --no-host-path --literal-ticks 0 > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err; stamp force_dist
+RGB_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --gpus 1 --steps 64 --warmup 16 --no-cpu-baseline --no-host-path --literal-ticks 0 > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err; stamp force_dist
 timeout 600 python tools/gpu_fuzz_rounds.py 40 12 2>&1 | tail -6 | tee $OUT/gpu_fuzz_rounds.txt; stamp fuzz
 python - $OUT <<'PY'
 import json, sys

@@ -18,7 +18,7 @@ for k in rw0 rw16 rw32 rw64 rw128 rd64; do
   $PC --pmc TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum TCP_GATE_EN1_sum -d $OUT/tcp_$k -o r06 -- $R/tools/probes/traffic_calib $k 4194304 > $OUT/tcp_$k.log 2>&1
 done
 stamp probes
-Q="--no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
+Q="--full --no-cpu-baseline --no-host-path --literal-ticks 0 --members 5"
 C="python $R/bench.py --steps 20 --warmup 20 $Q --check-ticks 0 --no-graph"
 P="timeout 150 rocprofv3 --kernel-trace --output-format csv --kernel-include-regex rgb_train_dealt"
 for v in base coop; do

@@ -7,7 +7,7 @@
 set -u
 TAG=${1:-ab}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-QUICK="--no-cpu-baseline --no-host-path --literal-ticks 0"
+QUICK="--full --no-cpu-baseline --no-host-path --literal-ticks 0"
 summ() {  # file label
   python - "$1" "$2" <<'PY'
 import json, sys

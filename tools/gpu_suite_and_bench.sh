@@ -7,7 +7,7 @@ t0=$(date +%s); stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" | tee -a $OUT/ti
 timeout 1200 python -m pytest tests -m gpu -q -x 2>&1 | tail -15 | tee $OUT/gpu_suite.txt; stamp suite
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a $OUT/gpu_suite.txt; stamp smoke
 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; stamp bench_driver
-timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; stamp bench
+timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; stamp bench
 python - $OUT <<'PY'
 import json, sys
 for name in ("bench_driver_form", "bench"):

@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 echo "$COMMIT" > $OUT/commit.txt
 cd /tmp && export TMPDIR=/tmp
 t0=$(date +%s); stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" | tee -a $OUT/timing.txt; }
-Q="--no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 0"
+Q="--full --no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 0"
 P="timeout 170 rocprofv3 --kernel-trace --output-format csv"
 $P --stats -d $OUT/stats -o $TAG -- python $R/bench.py --steps 20 --warmup 5 $Q > $OUT/stats.log 2>&1; stamp stats
 C240="python $R/bench.py --steps 240 --warmup 240 $Q --no-graph"
@@ -26,7 +26,7 @@ $P --pmc FETCH_SIZE -d $OUT/pmc_fetch_20 -o $TAG -- $C20 > $OUT/pmc_fetch_20.log
 $P --pmc WRITE_SIZE -d $OUT/pmc_write_20 -o $TAG -- $C20 > $OUT/pmc_write_20.log 2>&1
 stamp pmc20
 # literal config 5 (65 536 x 7, repair) as a train of rgb_train_dealt_kernel<7>: the headline shortened to nothing
-LIT="python $R/bench.py --steps 4 --warmup 2 --age 0 --no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 32 --no-graph"
+LIT="python $R/bench.py --full --steps 4 --warmup 2 --age 0 --no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 32 --no-graph"
 $P --stats -d $OUT/stats_lit -o $TAG -- $LIT > $OUT/stats_lit.log 2>&1
 $P --pmc FETCH_SIZE -d $OUT/pmc_fetch_lit -o $TAG -- $LIT > $OUT/pmc_fetch_lit.log 2>&1
 $P --pmc WRITE_SIZE -d $OUT/pmc_write_lit -o $TAG -- $LIT > $OUT/pmc_write_lit.log 2>&1
@@ -34,13 +34,13 @@ stamp pmc_lit
 cd $R
 python tools/make_traffic_json5.py $OUT $COMMIT > $OUT/traffic.json 2> $OUT/traffic.err
 RGB_TRAFFIC_TICKS=20 python tools/make_traffic_json5.py $OUT $COMMIT > $OUT/traffic20.json 2>> $OUT/traffic.err
-RGB_TRAFFIC_JSON=$OUT/traffic.json timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; stamp bench
-RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; stamp bench_driver
-B="--steps 20 --warmup 5 --no-cpu-baseline --no-host-path --literal-ticks 0"
+RGB_TRAFFIC_JSON=$OUT/traffic.json timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; stamp bench
+RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; stamp bench_driver
+B="--full --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --literal-ticks 0"
 RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 120 python bench.py $B --device-plan > $OUT/bench_driver_form_device_plan.json 2> $OUT/bench_driver_form_device_plan.err
 RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 120 python bench.py $B --train-form persistent > $OUT/bench_driver_form_persistent.json 2> $OUT/bench_driver_form_persistent.err
 timeout 120 python bench.py $B --launch tick > $OUT/bench_driver_form_tick.json 2> $OUT/bench_driver_form_tick.err
-RGB_TRAFFIC_JSON=$OUT/traffic.json timeout 120 python bench.py --steps 1000 --warmup 32 --no-cpu-baseline --no-host-path --literal-ticks 0 --device-plan > $OUT/bench_device_plan.json 2> $OUT/bench_device_plan.err
+RGB_TRAFFIC_JSON=$OUT/traffic.json timeout 120 python bench.py --full --steps 1000 --warmup 32 --no-cpu-baseline --no-host-path --literal-ticks 0 --device-plan > $OUT/bench_device_plan.json 2> $OUT/bench_device_plan.err
 stamp bench_forms
 python tools/pmc_summary.py $OUT > $OUT/pmc_summary.txt 2>&1
 [ -f ra_amd/csrc/variants/timeline.so ] && RGB_LIB=$R/ra_amd/csrc/variants/timeline.so TL_HINT=2 TL_AGE=512 TL_TICKS=32 timeout 200 python tools/train_timeline.py > $OUT/train_timeline.txt 2>&1

@@ -17,13 +17,13 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -8 | tee $OUT/gpu_suite.txt; stamp suite
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee -a $OUT/gpu_suite.txt; stamp smoke
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 0"
+Q="--full --no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 0"
 P="timeout 170 rocprofv3 --kernel-trace --output-format csv"
 $P --stats -d $OUT/stats -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 $Q > $OUT/stats.log 2>&1; stamp stats
 PK="$P --kernel-include-regex rgb_train"
 C240="python $R/bench.py --steps 240 --warmup 240 $Q --no-graph"
 C20="python $R/bench.py --steps 20 --warmup 20 $Q --no-graph"
-LIT="python $R/bench.py --steps 4 --warmup 2 --age 0 --no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 32 --no-graph"
+LIT="python $R/bench.py --full --steps 4 --warmup 2 --age 0 --no-cpu-baseline --no-host-path --check-ticks 0 --literal-ticks 32 --no-graph"
 pass() { # tag command counters...
   local tag=$1 cmd=$2; shift 2
   $PK --pmc "$@" -d $OUT/pmc_$tag -o $TAG -- $cmd > $OUT/pmc_$tag.log 2>&1
@@ -72,9 +72,9 @@ print(json.dumps({"what": "tools/probes/traffic_calib.hip: one request shape per
 PY
 python tools/make_traffic_json6.py $OUT $COMMIT > $OUT/traffic.json 2> $OUT/traffic.err
 RGB_TRAFFIC_TICKS=20 python tools/make_traffic_json6.py $OUT $COMMIT > $OUT/traffic20.json 2>> $OUT/traffic.err
-RGB_TRAFFIC_JSON=$OUT/traffic.json timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; stamp bench
-RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; stamp bench_driver
-B="--steps 20 --warmup 5 --no-cpu-baseline --no-host-path --literal-ticks 0"
+RGB_TRAFFIC_JSON=$OUT/traffic.json timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; stamp bench
+RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; stamp bench_driver
+B="--full --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --literal-ticks 0"
 for rep in 1 2; do
   RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 120 python bench.py $B > $OUT/bench_driver_form_quick_$rep.json 2> $OUT/bench_driver_form_quick_$rep.err
   RGB_TRAFFIC_JSON=$OUT/traffic20.json timeout 120 python bench.py $B --plan host > $OUT/bench_driver_form_host_plan_$rep.json 2> $OUT/bench_driver_form_host_plan_$rep.err
