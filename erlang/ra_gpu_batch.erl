@@ -39,6 +39,7 @@
 -define(MSG_HEARTBEAT_RPC, 13).
 -define(MSG_HEARTBEAT_REPLY, 14).
 -define(MSG_CONSISTENT_QUERY, 15).
+-define(MSG_TRANSFER_LEADERSHIP, 16).
 -define(NONE, 255).
 -define(UNDEF, 16#FFFFFFFFFFFFFFFF).
 
@@ -59,6 +60,14 @@
 -define(F_QUERY_APPLY, 67108864).
 -define(F_CANCEL_SNAPSHOT_RETRY, 134217728).
 -define(F_TRANSFER_LEADERSHIP, 536870912).
+-define(F_CALL_REPLY, 1073741824).
+%% reply_next_index under F_CALL_REPLY (RGB_CALL_* of the header)
+-define(CALL_OK, 0).
+-define(CALL_ALREADY_LEADER, 1).
+-define(CALL_UNKNOWN_MEMBER, 2).
+-define(CALL_NON_VOTER, 3).
+-define(CALL_NOT_UP_TO_DATE, 4).
+-define(CALL_UNSUPPORTED, 5).
 
 init() ->
     erlang:load_nif(filename:join(code:priv_dir(ra), "ra_gpu_batch_nif"), 0).
@@ -279,6 +288,10 @@ encode_msg(Server, {consistent_query, _From, _Fun}, _Slot) ->
     %% only while cluster_change_permitted; the QueryRef is queued by the caller under the
     %% query index the decision returns (reply_last_term)
     <<Server:32/little, ?MSG_CONSISTENT_QUERY:8, ?NONE:8, 0:8, 0:8, 0:(7 * 64)>>;
+encode_msg(Server, {transfer_leadership, Target}, Slot) ->
+    %% the leader_call of ra:transfer_leadership/2 (src/ra.erl:1156-1173); Slot(Target) = 255 for a server id that is
+    %% not a key of the cluster map (the device answers unknown_member)
+    <<Server:32/little, ?MSG_TRANSFER_LEADERSHIP:8, (Slot(Target)):8, 0:8, 0:8, 0:(7 * 64)>>;
 encode_msg(Server, pipeline_rpcs, _Slot) ->
     <<Server:32/little, ?MSG_PIPELINE_RPCS:8, ?NONE:8, 0:8, 0:8, 0:(7 * 64)>>;
 encode_msg(Server, tick_timeout, _Slot) ->
@@ -314,10 +327,23 @@ role(4) -> await_condition.
 %% Reconstitute the effects() list ra_server_proc:handle_effects/4 expects from a decision
 %% (reference src/ra_server.erl:178-206 for the vocabulary).  Id = this server's id,
 %% Member = fun(Slot) -> ra_server_id(); Member(first_peer) = the first key of the cluster map without Id
-%% (only asked for with F_TRANSFER_LEADERSHIP).
+%% (only asked for with F_TRANSFER_LEADERSHIP); Member(call) = the call message the decision answers (only asked for
+%% with F_CALL_REPLY and ?CALL_UNSUPPORTED).
 decision_to_effects(Id, Member, #{flags := F} = D) when F band ?F_INVARIANT =/= 0 ->
     %% the reference would have exited: do exactly that (reason by code, see the header)
     exit({ra_gpu_batch_invariant, Id, maps:get(invariant, D), Member});
+decision_to_effects(_Id, Member, #{flags := F, reply_next_index := Code, reply_to := To})
+  when F band ?F_CALL_REPLY =/= 0 ->
+    %% handle_leader({transfer_leadership, Target}, _) src/ra_server.erl:996-1035, in the reference's order; the
+    %% other roles' catch-all clause (:1186-1188, 1276-1278, 1655-1657).  The twin of ra_amd/effects.py call_reply/2
+    case Code of
+        ?CALL_OK -> [{reply, ok}, {send_msg, Member(To), election_timeout, cast}];
+        ?CALL_ALREADY_LEADER -> [{reply, already_leader}];
+        ?CALL_UNKNOWN_MEMBER -> [{reply, {error, unknown_member}}];
+        ?CALL_NON_VOTER -> [{reply, {error, non_voter}}];
+        ?CALL_NOT_UP_TO_DATE -> [{reply, {error, not_up_to_date}}];
+        ?CALL_UNSUPPORTED -> [{reply, {error, {unsupported_call, Member(call)}}}]
+    end;
 decision_to_effects(Id, Member, #{flags := F, reply_to := To} = D) ->
     Reply =
         if F band ?F_REPLY =:= 0 -> [];

@@ -5,7 +5,7 @@
  * handle_candidate/2, handle_pre_vote/2 and handle_await_condition/2 for
  * the message classes append_entries_rpc / append_entries_reply /
  * request_vote_rpc / request_vote_result / {ra_log_event,{written,..}} /
- * pipeline_rpcs / {commands,..}.
+ * pipeline_rpcs / {commands,..} / the call {transfer_leadership, Target}.
  *
  * This header is the drop-in boundary.  The call site
  * it replaces is ra_server_proc:handle_raft_state/3 and handle_leader/2
@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGB_ABI_VERSION   9u
+#define RGB_ABI_VERSION   10u
 #define RGB_UNDEF         UINT64_MAX   /* Erlang 'undefined' (index or term)            */
 #define RGB_NONE          0xFFu        /* undefined ra_server_id() (member slot)        */
 #define RGB_MAX_MEMBERS   8u           /* members per Raft group held on the device     */
@@ -60,12 +60,19 @@ enum {
                                   role await_condition with this reason and the log as it was BEFORE the write; from then on
                                   it sets RGB_MF_CAN_WRITE on the server's messages once ra_log:can_write/1 is true again --
                                   the predicate of the reference.  No stored reply: a timeout just returns to follower. */
-  RGB_COND_WAL_DOWN_LEADER = 4 /* leader whose ra_log:append/2 raised wal_down on a {command, _} (src/ra_server.erl:655-672):
+  RGB_COND_WAL_DOWN_LEADER = 4, /* leader whose ra_log:append/2 raised wal_down on a {command, _} (src/ra_server.erl:655-672):
                                   the same predicate (RGB_MF_CAN_WRITE), but the condition carries transition_to => leader
                                   and a timeout that also returns to leader with [{next_event, cast, {transfer_leadership,
                                   Peer}}] (RGB_F_TRANSFER_LEADERSHIP) when the log still cannot be written.  The append is
                                   host I/O: the host re-uploads the server as it was BEFORE the command, in role
                                   await_condition with this reason (test/ra_server_SUITE.erl:1035-1073, vector W2).       */
+  RGB_COND_TRANSFER_LEADERSHIP = 5 /* leader that accepted {transfer_leadership, Target} (src/ra_server.erl:1008-1035): the
+                                  predicate is transfer_leadership_condition/2 (:2235-2245) -- an append_entries_rpc of a
+                                  higher term releases the server to FOLLOWER (the condition has no top-level
+                                  transition_to), which re-processes it; every other message is dropped.  The timeout map
+                                  is #{effects => [], transition_to => leader}: await_condition_timeout returns to leader
+                                  with no effects.  Entered on the device (RGB_MSG_TRANSFER_LEADERSHIP); the
+                                  install_snapshot_rpc arm of the predicate is the host's (no device kind carries it) */
 };
 
 /* message kinds (one inbound ra_msg() for one server) */
@@ -86,12 +93,15 @@ enum {
                                     src/ra_log.erl:1054-1150: the log prefix up to Idx is released */
   RGB_MSG_HEARTBEAT_RPC    = 13, /* #heartbeat_rpc{}         src/ra.hrl:193-196                    */
   RGB_MSG_HEARTBEAT_REPLY  = 14, /* {Peer,#heartbeat_reply{}} src/ra.hrl:198-200                   */
-  RGB_MSG_CONSISTENT_QUERY = 15  /* {consistent_query,_,_} / {consistent_aux,_,_} with
+  RGB_MSG_CONSISTENT_QUERY = 15, /* {consistent_query,_,_} / {consistent_aux,_,_} with
                                     cluster_change_permitted = true  src/ra_server.erl:855-860, 868-873:
                                     the query itself (a fun) stays queued on the host under the
                                     query_index the decision returns                               */
+  RGB_MSG_TRANSFER_LEADERSHIP = 16 /* the call {transfer_leadership, Target} (ra:transfer_leadership/2 src/ra.erl:1156-1173
+                                    -> ra_server_proc:leader_call :265-268; src/ra_server.erl:996-1035): answered with
+                                    RGB_F_CALL_REPLY.  Shares class rank 14 with RGB_MSG_CONSISTENT_QUERY          */
 };
-#define RGB_MSG_KIND_MAX RGB_MSG_CONSISTENT_QUERY
+#define RGB_MSG_KIND_MAX RGB_MSG_TRANSFER_LEADERSHIP
 #define RGB_PROTO_VERSION 1u    /* ?RA_PROTO_VERSION src/ra.hrl:107 */
 
 /* rgb_msg.flags */
@@ -132,6 +142,8 @@ enum {
  *   HEARTBEAT_RPC term, from=leader_id, a=query_index
  *   HEARTBEAT_REPLY term, from=peer, a=query_index
  *   CONSISTENT_QUERY (no fields)
+ *   TRANSFER_LEADERSHIP from=the target's member slot; RGB_NONE = a server id that is not a key of the cluster
+ *                 map (no other field is used)
  */
 typedef struct rgb_msg {
   uint32_t server;      /* target server id = group * n_members + member slot */
@@ -194,10 +206,27 @@ typedef struct rgb_msg {
                                                not writable: [{next_event, cast, {transfer_leadership, PeerId}}] where PeerId is
                                                the host's hd(maps:to_list(maps:remove(Self, Cluster))) -- raised only when the
                                                cluster has another member (src/ra_server.erl:660-668, 1932-1945)           */
+#define RGB_F_CALL_REPLY     (1u << 30) /* {reply, Reply} to the caller of a call (RGB_MSG_TRANSFER_LEADERSHIP): the code RGB_CALL_*
+                                           is in reply_next_index.  RGB_CALL_OK: [{reply, ok}, {send_msg, Target,
+                                           election_timeout, cast}] with Target = reply_to -- the reference emits the two
+                                           together (test/ra_server_SUITE.erl:1127-1131); any other code: the single error
+                                           reply, reply_to = RGB_NONE.  Never in the compact form                     */
 #define RGB_F_COMPACT        (1u << 28) /* DEVICE-RESIDENT decision streams only (rgb_run_ticks_device, rgb_train_run_device,
                                            the generator's apply): only the first 32 bytes of this 64-byte slot were written
                                            -- the compact form below; rgb_decision_expand() gives the record back.
                                            rgb_collect always hands out full records (expanded on the device) */
+
+/* rgb_decision.reply_next_index under RGB_F_CALL_REPLY: the reply of handle_leader/2 to {transfer_leadership, Target}
+ * (src/ra_server.erl:996-1035), checked in this order, or of the other roles' catch-all clause */
+enum {
+  RGB_CALL_OK             = 0, /* ok: the leader now awaits RGB_COND_TRANSFER_LEADERSHIP           :1019-1029 */
+  RGB_CALL_ALREADY_LEADER = 1, /* already_leader: Target is the leader itself                      :996-1000  */
+  RGB_CALL_UNKNOWN_MEMBER = 2, /* {error, unknown_member}: Target is not a key of the cluster map  :1001-1007 */
+  RGB_CALL_NON_VOTER      = 3, /* {error, non_voter}: Target's membership =/= voter                :1012-1016 */
+  RGB_CALL_NOT_UP_TO_DATE = 4, /* {error, not_up_to_date}: Target's next_index =/= ra_log:next_index/1 :1030-1033 */
+  RGB_CALL_UNSUPPORTED    = 5  /* {error, {unsupported_call, Msg}}: follower, candidate, pre_vote
+                                  (:1186-1188, 1276-1278, 1655-1657)                                            */
+};
 
 /* rgb_decision.invariant: exit reasons / failed assertions of the reference */
 enum {

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 CFG_ROUNDS_PER_LAUNCH = 1      # rgb_config.flags: rgb_submit launches one kernel per sub-tick round (the default since round 5)
 CFG_SUBMIT_TRAINS = 16         # rgb_config.flags: opt-in -- rgb_submit fuses the sub-tick rounds of a batch into one train launch
 CFG_FUSE_PIPELINE = 4          # rgb_config.flags: a leader's success reply / written event carries its pipeline_rpcs event's rpcs (opt-in)
@@ -24,17 +24,19 @@ DEFAULT_MAX_PIPELINE_COUNT = 4096
 # ra_state()
 ROLE_FOLLOWER, ROLE_CANDIDATE, ROLE_LEADER, ROLE_PRE_VOTE, ROLE_AWAIT_CONDITION = range(5)
 ROLE_NAMES = ["follower", "candidate", "leader", "pre_vote", "await_condition"]
-COND_NONE, COND_MISSING, COND_TERM_MISMATCH, COND_WAL_DOWN, COND_WAL_DOWN_LEADER = range(5)
+(COND_NONE, COND_MISSING, COND_TERM_MISMATCH, COND_WAL_DOWN, COND_WAL_DOWN_LEADER,
+ COND_TRANSFER_LEADERSHIP) = range(6)
 
 (MSG_NOP, MSG_AER, MSG_AER_REPLY, MSG_REQUEST_VOTE, MSG_VOTE_RESULT, MSG_WRITTEN,
  MSG_PIPELINE_RPCS, MSG_APPEND, MSG_AWAIT_TIMEOUT, MSG_ELECTION_TIMEOUT, MSG_PRE_VOTE_RPC,
  MSG_PRE_VOTE_RESULT, MSG_SNAPSHOT_WRITTEN, MSG_HEARTBEAT_RPC, MSG_HEARTBEAT_REPLY,
- MSG_CONSISTENT_QUERY) = range(16)
-N_KINDS = 16
+ MSG_CONSISTENT_QUERY, MSG_TRANSFER_LEADERSHIP) = range(17)
+N_KINDS = 17
 PROTO_VERSION = 1
 # device order of a tick: clause family = (class rank of the kind, success flag); the four hot
-# kinds first (each has a specialised kernel), the rest after (ra_amd/csrc/rgb_internal.h)
-KIND_RANK = np.array([15, 0, 1, 5, 6, 2, 4, 3, 7, 8, 9, 10, 11, 12, 13, 14], dtype=np.int64)
+# kinds first (each has a specialised kernel), the rest after (ra_amd/csrc/rgb_internal.h); the two cold
+# leader-side calls (consistent query, transfer_leadership) share rank 14
+KIND_RANK = np.array([15, 0, 1, 5, 6, 2, 4, 3, 7, 8, 9, 10, 11, 12, 13, 14, 14], dtype=np.int64)
 MF_SUCCESS = 0x01
 MF_FORCE = 0x02
 MF_TICK = 0x04
@@ -72,6 +74,10 @@ F_QUERY_APPLY = 1 << 26
 F_CANCEL_SNAPSHOT_RETRY = 1 << 27
 F_TRANSFER_LEADERSHIP = 1 << 29   # leader's wal_down condition timed out: {transfer_leadership, Peer} (src/ra_server.erl:660-668)
 F_COMPACT = 1 << 28   # device-resident decision streams: the 32-byte compact form (expand_decisions)
+F_CALL_REPLY = 1 << 30   # {reply, Reply} to a call's caller: CALL_* in reply_next_index, CALL_OK's send_msg target in reply_to
+
+# rgb_decision.reply_next_index under F_CALL_REPLY: handle_leader({transfer_leadership, T}, _) src/ra_server.erl:996-1035
+(CALL_OK, CALL_ALREADY_LEADER, CALL_UNKNOWN_MEMBER, CALL_NON_VOTER, CALL_NOT_UP_TO_DATE, CALL_UNSUPPORTED) = range(6)
 
 (INV_NONE, INV_LEADER_SAW_AER_SAME_TERM, INV_TRUNCATE_BELOW_APPLIED, INV_WRITE_BELOW_APPLIED,
  INV_MISMATCH_TERM_UNDEFINED, INV_WRITE_INTEGRITY, INV_SET_LAST_INDEX_NOT_FOUND,

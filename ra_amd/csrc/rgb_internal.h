@@ -80,7 +80,8 @@ typedef uint32_t u32;
 #define PK_VOTES_SH     9   /* 4 */
 #define PK_NRUNS_SH     13  /* 5 */
 #define PK_NONVOTER_SH  18  /* 1 */
-#define PK_CONDTO_SH    19  /* 1: the stored condition's transition_to is leader (RGB_COND_WAL_DOWN_LEADER = COND 3 + this bit) */
+#define PK_CONDTO_SH    19  /* 1: the stored condition's transition_to is leader (RGB_COND_WAL_DOWN_LEADER = COND 3 + this bit;
+                               RGB_COND_TRANSFER_LEADERSHIP = COND 0 + this bit: pk_cond_reason / pk_with_cond_reason) */
 #define PK_VOTED_SH     20  /* 4, 0xF = undefined */
 #define PK_LEADER_SH    24  /* 4, 0xF = undefined */
 #define PK_CONDLDR_SH   28  /* 4, 0xF = undefined */
@@ -91,6 +92,16 @@ typedef uint32_t u32;
 #define PK_QPEER_SH     57  /* 1: some peer query_index > 0 (reset_query_index has work) */
 #define PK_BACKOFF_SH   58  /* 1: some peer is in {snapshot_backoff,_}: qry row word QRY_BACKOFF holds the mask */
 #define PK_PENDX_SH     59  /* 1: `pending` has ranges below its newest one: qry row words QRY_PEND_LO.. hold them */
+/* the condition field (COND 2 bits, CONDTO 1 bit) <-> rgb_server_state.cond_reason */
+static inline __host__ __device__ unsigned pk_cond_reason(u64 pk) {
+  const unsigned c = (unsigned)((pk >> PK_COND_SH) & 3ull), to = (unsigned)((pk >> PK_CONDTO_SH) & 1ull);
+  return to == 0u ? c : c == RGB_COND_WAL_DOWN ? (unsigned)RGB_COND_WAL_DOWN_LEADER : (unsigned)RGB_COND_TRANSFER_LEADERSHIP;
+}
+static inline __host__ __device__ u64 pk_with_cond_reason(u64 pk, unsigned reason) {
+  const u64 c = reason == RGB_COND_WAL_DOWN_LEADER ? (u64)RGB_COND_WAL_DOWN : reason == RGB_COND_TRANSFER_LEADERSHIP ? 0ull : (u64)reason;
+  const u64 to = (reason == RGB_COND_WAL_DOWN_LEADER || reason == RGB_COND_TRANSFER_LEADERSHIP) ? 1ull : 0ull;
+  return (pk & ~((3ull << PK_COND_SH) | (1ull << PK_CONDTO_SH))) | (c << PK_COND_SH) | (to << PK_CONDTO_SH);
+}
 #define QRY_PEND_LO     12  /* (first, last) of the lower old range, (1, 0) when there is only one */
 #define QRY_PEND_HI     14  /* (first, last) of the old range next below the newest range [HOT_PEND .. last_index] */
 #define QRY_BACKOFF     9   /* qry row: word 0 query_index, 1..8 peer query_index, 9 backoff mask */
@@ -118,6 +129,7 @@ static inline __host__ __device__ unsigned rgb_kind_rank(unsigned kind) {
     case RGB_MSG_HEARTBEAT_RPC: return 12;
     case RGB_MSG_HEARTBEAT_REPLY: return 13;
     case RGB_MSG_CONSISTENT_QUERY: return 14;
+    case RGB_MSG_TRANSFER_LEADERSHIP: return 14;   /* two cold leader-side calls share the class */
     default: return 15;   /* NOP */
   }
 }

@@ -718,6 +718,16 @@ __device__ __forceinline__ void pre_vote_reply(Lane &L, u64 term, u64 token, boo
   L.reply_to = to8;
 }
 
+/* {reply, Reply} to the caller of a call (RGB_F_CALL_REPLY): the code in reply_next_index, reply_to = the target of
+ * the {send_msg, Target, election_timeout, cast} that goes with RGB_CALL_OK (RGB_NONE otherwise) */
+template <class Lane>
+__device__ __forceinline__ void call_reply(Lane &L, unsigned code, unsigned to8) {
+  L.has_reply = true;
+  L.flags |= RGB_F_CALL_REPLY;
+  L.r_term = 0; L.r_next = code; L.r_last = 0; L.r_lterm = 0;
+  L.reply_to = to8;
+}
+
 /* required_quorum/1 (src/ra_server.erl:3996-3999), count_voters/1 :4001-4009 */
 template <class Lane>
 __device__ __forceinline__ unsigned required_quorum(const Lane &L) {
@@ -1563,6 +1573,9 @@ __device__ __forceinline__ int handle_follower(Lane &L) {
       return 0;
     case RGB_MSG_HEARTBEAT_REPLY: update_term(L, L.term); return 0;  /* :1534-1537 */
     case RGB_MSG_PRE_VOTE_RESULT: return 0;                          /* :1612-1614 */
+    case RGB_MSG_TRANSFER_LEADERSHIP:
+      call_reply(L, RGB_CALL_UNSUPPORTED, RGB_NONE);                 /* :1655-1657 */
+      return 0;
     case RGB_MSG_PRE_VOTE_RPC:
       if (pk_get(L.pk, PK_NONVOTER_SH, 1)) return 0;                 /* :1475-1480 */
       return process_pre_vote(L);                                    /* :1481-1482 */
@@ -1743,6 +1756,23 @@ __device__ __forceinline__ int handle_leader(Lane &L, bool &reprocess, const rgb
     case RGB_MSG_SNAPSHOT_WRITTEN:                                   /* :745-747 */
       log_snapshot_written(L, L.a, L.b);
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP: {
+      const unsigned target = L.from;
+      if (target == self_of(L)) { call_reply(L, RGB_CALL_ALREADY_LEADER, RGB_NONE); return 0; }   /* :996-1000 */
+      if (!present(L, target)) { call_reply(L, RGB_CALL_UNKNOWN_MEMBER, RGB_NONE); return 0; }    /* :1001-1007 */
+      if (!voter(L, target)) { call_reply(L, RGB_CALL_NON_VOTER, RGB_NONE); return 0; }           /* :1012-1016 */
+      if (!PL) load_peers<N>(L);
+      if (ni_of<N, PL>(L, target) != next_log_index(L)) {                                       /* :1017-1018 */
+        call_reply(L, RGB_CALL_NOT_UP_TO_DATE, RGB_NONE);                                        /* :1030-1033 */
+        return 0;
+      }
+      /* :1019-1029: await_condition with transfer_leadership_condition/2 and the timeout map
+       * #{effects => [], transition_to => leader}; [{reply, ok}, {send_msg, Target, election_timeout, cast}] */
+      L.pk = pk_with_cond_reason(L.pk, RGB_COND_TRANSFER_LEADERSHIP);
+      set_role(L, RGB_ROLE_AWAIT_CONDITION);
+      call_reply(L, RGB_CALL_OK, target);
+      return 0;
+    }
     default: L.flags |= RGB_F_UNHANDLED; return 0;
   }
 }
@@ -1823,6 +1853,9 @@ __device__ __forceinline__ int handle_candidate(Lane &L, bool &reprocess) {
     case RGB_MSG_ELECTION_TIMEOUT:
       call_for_election_candidate<N>(L);                             /* :1161-1162 */
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP:
+      call_reply(L, RGB_CALL_UNSUPPORTED, RGB_NONE);                 /* :1186-1188 */
+      return 0;
     default: L.flags |= RGB_F_UNHANDLED; return 0;
   }
 }
@@ -1895,6 +1928,9 @@ __device__ __forceinline__ int handle_pre_vote(Lane &L, bool &reprocess) {
     case RGB_MSG_ELECTION_TIMEOUT:
       call_for_election_pre_vote<N>(L, L.c);                         /* :1255-1256 */
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP:
+      call_reply(L, RGB_CALL_UNSUPPORTED, RGB_NONE);                 /* :1276-1278 */
+      return 0;
     default: L.flags |= RGB_F_UNHANDLED; return 0;
   }
 }
@@ -1904,8 +1940,11 @@ template <int N, class Lane>
 __device__ __forceinline__ int handle_await_condition(Lane &L, bool &reprocess, const u64 *cond_row) {
   /* wal_down_condition/2 :2232-2233: the predicate is ra_log:can_write/1, which the host knows and passes along.
    * The follower's condition (:1377-1385) has no transition_to and no timeout map (follower, no effects); the leader's
-   * (:660-668, PK_CONDTO) goes back to leader, on a timeout with [{next_event, cast, {transfer_leadership, Peer}}] */
+   * (:660-668, PK_CONDTO) goes back to leader, on a timeout with [{next_event, cast, {transfer_leadership, Peer}}].
+   * transfer_leadership_condition/2 :2235-2245 (entered at :1019-1029): a higher-term append_entries_rpc releases the
+   * server to follower (no top-level transition_to), the timeout map returns it to leader with no effects */
   const bool wal_down = pk_get(L.pk, PK_COND_SH, 2) == RGB_COND_WAL_DOWN;
+  const bool transfer = pk_cond_reason(L.pk) == RGB_COND_TRANSFER_LEADERSHIP;
   const bool can_write = (L.mflags & RGB_MF_CAN_WRITE) != 0;
   const unsigned back = pk_get(L.pk, PK_CONDTO_SH, 1) ? RGB_ROLE_LEADER : RGB_ROLE_FOLLOWER;
   switch (L.kind) {
@@ -1919,6 +1958,10 @@ __device__ __forceinline__ int handle_await_condition(Lane &L, bool &reprocess, 
             (pk_get(L.pk, PK_PRESENT_SH, 8) & ~(1ull << self_of(L))) != 0ull)
           L.flags |= RGB_F_TRANSFER_LEADERSHIP;
         set_role(L, back);
+        return 0;
+      }
+      if (transfer) {                    /* :1932-1945: predicate false -> #{effects => [], transition_to => leader} */
+        set_role(L, RGB_ROLE_LEADER);
         return 0;
       }
       /* :1932-1945: predicate false -> stored effects, back to follower */
@@ -1945,6 +1988,8 @@ __device__ __forceinline__ int handle_await_condition(Lane &L, bool &reprocess, 
       bool pred = false;
       if (wal_down) {
         pred = can_write;
+      } else if (transfer) {
+        pred = L.term > L.ct;                                        /* :2235-2238 */
       } else if (L.term >= L.ct) {
         int h = has_log_entry_or_snapshot(L, L.a, L.b);
         if (h == HLE_OK) pred = true;
@@ -1954,8 +1999,8 @@ __device__ __forceinline__ int handle_await_condition(Lane &L, bool &reprocess, 
       return 0;
     }
     default:
-      /* the catch-all clause :1950-1959: follower_catchup_cond/3 is false for anything but an append_entries_rpc;
-       * the wal_down predicate does not look at the message */
+      /* the catch-all clause :1950-1959: follower_catchup_cond/3 and transfer_leadership_condition/2 (:2243-2244) are
+       * false for anything but an append_entries_rpc; the wal_down predicate does not look at the message */
       if (wal_down && can_write) { set_role(L, back); reprocess = true; }
       return 0;
   }
@@ -2105,7 +2150,8 @@ __device__ __forceinline__ void process_message(const rgb_dev &dev, const ulongl
 #endif
   constexpr bool PL = (TR ? RGB_X_PL : RGB_X_PL_TICK) && PRE && rgb_class_slice(1, (unsigned)N) == 32u &&
                       (KIND == RGB_MSG_AER_REPLY || KIND == RGB_MSG_APPEND || KIND == RGB_MSG_PIPELINE_RPCS);
-  if (!PL && (L.kind == RGB_MSG_AER_REPLY || L.kind == RGB_MSG_APPEND || L.kind == RGB_MSG_PIPELINE_RPCS) &&
+  if (!PL && (L.kind == RGB_MSG_AER_REPLY || L.kind == RGB_MSG_APPEND || L.kind == RGB_MSG_PIPELINE_RPCS ||
+              L.kind == RGB_MSG_TRANSFER_LEADERSHIP) &&
       !RGB_KNOB(dev, 64u)) {
     load_peers<N>(L);      /* from memory (the class kernel touched the row's line with the hot-line fetch) */
   }
@@ -3112,9 +3158,13 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
       RGB_CASE(8, RGB_MSG_ELECTION_TIMEOUT) RGB_CASE(9, RGB_MSG_PRE_VOTE_RPC)
       RGB_CASE(10, RGB_MSG_PRE_VOTE_RESULT) RGB_CASE(11, RGB_MSG_SNAPSHOT_WRITTEN)
       RGB_CASE(12, RGB_MSG_HEARTBEAT_RPC) RGB_CASE(13, RGB_MSG_HEARTBEAT_REPLY)
-      default:
-        process_message<N, RGB_MSG_CONSISTENT_QUERY, PRE, TR>(dev, m0, m1, m2, m3, base + lane, rpcs, rpc_slot_base,
-                                                              msg_index_base, d, tlp, hrow, hswz, prow);
+      default:     /* class 14: the two cold leader-side calls, each through its own clause-folded path */
+        if (((m0.x >> 32) & 0xFFull) == RGB_MSG_TRANSFER_LEADERSHIP)
+          process_message<N, RGB_MSG_TRANSFER_LEADERSHIP, PRE, TR>(dev, m0, m1, m2, m3, base + lane, rpcs, rpc_slot_base,
+                                                                   msg_index_base, d, tlp, hrow, hswz, prow);
+        else
+          process_message<N, RGB_MSG_CONSISTENT_QUERY, PRE, TR>(dev, m0, m1, m2, m3, base + lane, rpcs, rpc_slot_base,
+                                                                msg_index_base, d, tlp, hrow, hswz, prow);
         break;
     }
 #undef RGB_CASE
@@ -3978,8 +4028,7 @@ __global__ void rgb_pack_kernel(rgb_dev dev, const rgb_server_state *__restrict_
   }
   u64 pk = 0;
   pk = pk_set(pk, PK_ROLE_SH, 3, h.role);
-  pk = pk_set(pk, PK_COND_SH, 2, h.cond_reason == RGB_COND_WAL_DOWN_LEADER ? RGB_COND_WAL_DOWN : h.cond_reason);
-  pk = pk_set(pk, PK_CONDTO_SH, 1, h.cond_reason == RGB_COND_WAL_DOWN_LEADER ? 1 : 0);
+  pk = pk_with_cond_reason(pk, h.cond_reason);
   pk = pk_set(pk, PK_SELF_SH, 4, h.self);
   pk = pk_set(pk, PK_VOTES_SH, 4, h.votes);
   pk = pk_set(pk, PK_NRUNS_SH, 5, nr);
@@ -4054,7 +4103,7 @@ __global__ void rgb_unpack_kernel(rgb_dev dev, rgb_server_state *__restrict__ ou
   if (!(h.first_index <= h.last_index)) { nr = 0; h.first_index = h.last_index + 1; }
   for (unsigned r = 0; r < nr && r < RGB_MAX_RUNS; ++r) { h.run_start[r] = runs[2 * r]; h.run_term[r] = runs[2 * r + 1]; }
   h.role = (uint8_t)pk_get(pk, PK_ROLE_SH, 3);
-  h.cond_reason = (uint8_t)(pk_get(pk, PK_COND_SH, 2) + pk_get(pk, PK_CONDTO_SH, 1));   /* 3 + 1 = RGB_COND_WAL_DOWN_LEADER */
+  h.cond_reason = (uint8_t)pk_cond_reason(pk);
   h.self = (uint8_t)pk_get(pk, PK_SELF_SH, 4);
   h.n_members = (uint8_t)N;
   h.voted_for = (uint8_t)slot4to8((unsigned)pk_get(pk, PK_VOTED_SH, 4));
@@ -4138,7 +4187,7 @@ __global__ void rgb_checksum_kernel(rgb_dev dev, u32 first, u32 n, u64 *__restri
   x = fnv_word(x, li); x = fnv_word(x, hot[HOT_LT]); x = fnv_word(x, hot[HOT_LWI]);
   x = fnv_word(x, hot[HOT_LWT]); x = fnv_word(x, hot[HOT_SI]); x = fnv_word(x, hot[HOT_ST]);
   x = fnv_word(x, fi);
-  u64 packed = pk_get(pk, PK_ROLE_SH, 3) | ((pk_get(pk, PK_COND_SH, 2) + pk_get(pk, PK_CONDTO_SH, 1)) << 8) |
+  u64 packed = pk_get(pk, PK_ROLE_SH, 3) | ((u64)pk_cond_reason(pk) << 8) |
                (pk_get(pk, PK_SELF_SH, 4) << 16) | ((u64)N << 24) |
                ((u64)slot4to8((unsigned)pk_get(pk, PK_VOTED_SH, 4)) << 32) |
                ((u64)slot4to8((unsigned)pk_get(pk, PK_LEADER_SH, 4)) << 40) |

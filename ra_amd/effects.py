@@ -110,6 +110,11 @@ class ElectionTimeout:
     token: int = 0                           # the make_ref() of call_for_election(pre_vote, _)
 
 
+@dataclass(frozen=True)
+class TransferLeadership:                    # the call {transfer_leadership, Target} (src/ra_server.erl:996-1035)
+    target: "int | None"                     # member slot; None = a server id that is not a key of the cluster map
+
+
 PIPELINE_RPCS = "pipeline_rpcs"
 TICK_TIMEOUT = "tick_timeout"
 AWAIT_CONDITION_TIMEOUT = "await_condition_timeout"
@@ -178,6 +183,8 @@ def encode(server: int, record, from_slot: int = abi.NONE) -> np.void:
     elif isinstance(r, ElectionTimeout):
         m = _blank(server, abi.MSG_ELECTION_TIMEOUT)
         m["c"] = r.token
+    elif isinstance(r, TransferLeadership):
+        m = _blank(server, abi.MSG_TRANSFER_LEADERSHIP, abi.NONE if r.target is None else r.target)
     elif r == PIPELINE_RPCS:
         m = _blank(server, abi.MSG_PIPELINE_RPCS)
     elif r == TICK_TIMEOUT:
@@ -213,6 +220,24 @@ def split_entries(rpc: AppendEntriesRpc) -> List[AppendEntriesRpc]:
     return out
 
 
+CALL_REPLIES = {abi.CALL_ALREADY_LEADER: "already_leader", abi.CALL_UNKNOWN_MEMBER: ("error", "unknown_member"),
+                abi.CALL_NON_VOTER: ("error", "non_voter"), abi.CALL_NOT_UP_TO_DATE: ("error", "not_up_to_date")}
+
+
+def call_reply(msg, dec) -> list:
+    """The effects of a RGB_F_CALL_REPLY decision, in the reference's order: [{reply, ok}, {send_msg, Target,
+    election_timeout, cast}] (src/ra_server.erl:1019-1029), or the single reply of :996-1016 / :1030-1033, or
+    {reply, {error, {unsupported_call, Msg}}} of the other roles (:1186-1188, 1276-1278, 1655-1657)."""
+    code = int(dec["reply_next_index"])
+    if code == abi.CALL_OK:
+        return [("reply", "ok"), ("send_msg", int(dec["reply_to"]), "election_timeout", "cast")]
+    if code == abi.CALL_UNSUPPORTED:
+        target = int(msg["from"])
+        call = ("transfer_leadership", None if target == abi.NONE else target)
+        return [("reply", ("error", ("unsupported_call", call)))]
+    return [("reply", CALL_REPLIES[code])]
+
+
 def decode(msg, dec, rpcs, state_after, n_members: int) -> list:
     """effects() of one transition, in the reference's vocabulary.  `rpcs` = the rgb_rpc records whose
     msg_index is this message; `state_after` = the server's row after the transition (the leader's log
@@ -224,6 +249,8 @@ def decode(msg, dec, rpcs, state_after, n_members: int) -> list:
     fx: list = []
     if fl & abi.F_INVARIANT:
         return [("exit", int(dec["invariant"]))]
+    if fl & abi.F_CALL_REPLY:
+        fx.extend(call_reply(msg, dec))
     if fl & abi.F_REPLY:
         if fl & abi.F_REPLY_VOTE:
             fx.append(("reply", RequestVoteResult(int(dec["reply_term"]), ok)))

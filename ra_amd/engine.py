@@ -634,7 +634,7 @@ class TrainPlan:
 
 def train_bucket(kind, flags, server, n_members):
     """rgb_train_bucket over numpy arrays: (class rank of the kind, group mod 8, success flag)."""
-    rank = np.array([15, 0, 1, 5, 6, 2, 4, 3, 7, 8, 9, 10, 11, 12, 13, 14], dtype=np.uint32)[np.asarray(kind) & 15]
+    rank = np.append(abi.KIND_RANK, 15).astype(np.uint32)[np.minimum(np.asarray(kind), abi.N_KINDS)]   # unknown: NOP
     shard = (np.asarray(server, dtype=np.uint32) // n_members) & 7
     return (rank * 8 + shard) * 2 + (np.asarray(flags, dtype=np.uint32) & 1)
 

@@ -20,7 +20,9 @@ messages with ra_amd.effects -- the same routing erlang/ra_gpu_batch.erl does fo
   * RGB_F_WROTE / commands: payloads go into the member's log, a `written` event follows (the WAL
     stand-in confirms on the next tick);
   * RGB_F_APPLIED: entries last_applied_before+1 .. last_applied are applied to the member's machine;
-  * replies, vote requests, heartbeats, pipeline_rpcs, the post-election noop: as in the reference.
+  * replies, vote requests, heartbeats, pipeline_rpcs, the post-election noop: as in the reference;
+  * transfer_leadership (a call): the reply goes to the caller's Call; with `ok` the leader's
+    {send_msg, Target, election_timeout, cast} posts an election timeout (fresh token) to the target.
 
 Loopback transport only (all members live in this process), in-memory logs, no snapshots: this is the
 caller of the hot path, small enough to read, not a storage engine.  Delivery is reliable and FIFO per
@@ -54,6 +56,13 @@ class KvMachine:
             self.state.pop(command[1], None)
 
 
+class Call:
+    """A call posted to a server: `reply` is None until the server's decision answers it."""
+
+    def __init__(self, server: int, request):
+        self.server, self.request, self.reply = server, request, None
+
+
 class RaShell:
     def __init__(self, engine, n_groups: int, n_members: int, machine: Callable[[], object] = KvMachine):
         self.eng, self.G, self.N = engine, n_groups, n_members
@@ -63,6 +72,7 @@ class RaShell:
         self.machines = [machine() for _ in range(self.S)]
         self.pending_commands: List[deque] = [deque() for _ in range(self.S)]  # payloads of queued Commands
         self.token = 0
+        self.calls: List[deque] = [deque() for _ in range(self.S)]       # Calls posted to a server, oldest first
         self.down: set = set()                        # partitioned members: nothing in, nothing out
         self.state = engine.get_state()
         self.ticks = 0
@@ -96,12 +106,34 @@ class RaShell:
             if int(self.state[s]["role"]) == abi.ROLE_LEADER:
                 self._post(s, fx.encode(s, fx.TICK_TIMEOUT))
 
+    def transfer_leadership(self, group: int, target: Optional[int]) -> Optional[Call]:
+        """ra:transfer_leadership(Leader, Target) (src/ra.erl:1156-1173): the call to the group's leader; None when
+        the group has none right now.  `target` is a member slot (None: not a member).  The returned Call's
+        `reply` is the reference's reply once a tick has decided it: "ok", "already_leader" or ("error", Reason)."""
+        lead = self.leader_of(group)
+        if lead is None:
+            return None
+        s = group * self.N + lead
+        call = Call(s, fx.TransferLeadership(target))
+        if s not in self.down:
+            self.calls[s].append(call)
+        self._post(s, fx.encode(s, call.request))
+        return call
+
+    def await_condition_timeouts(self):
+        """The await_condition state timeout (src/ra_server_proc.erl:1115-1121) on every server in await_condition:
+        await_condition_timeout ends the condition its own way (a transfer: back to leader)."""
+        for s in range(self.S):
+            if int(self.state[s]["role"]) == abi.ROLE_AWAIT_CONDITION:
+                self._post(s, fx.encode(s, fx.AWAIT_CONDITION_TIMEOUT))
+
     # ---------------------------------------------------------------- the loop
     def partition(self, group: int, member: int):
         """Cut one member off: its mailbox is discarded and nothing reaches it until heal()."""
         s = group * self.N + member
         self.down.add(s)
         self.mailbox[s].clear()
+        self.calls[s].clear()
 
     def heal(self, group: int, member: int):
         self.down.discard(group * self.N + member)
@@ -148,6 +180,8 @@ class RaShell:
         peer = lambda slot: g * self.N + int(slot)
         fl, kind = int(d["flags"]), int(m["kind"])
         log = self.logs[s]
+        # the call this message is (a server in await_condition drops it unanswered: the Call keeps reply None)
+        call = self.calls[s].popleft() if kind == abi.MSG_TRANSFER_LEADERSHIP and self.calls[s] else None
         # the log writes of this transition (payloads stay here; the engine moved the cursors)
         if kind == abi.MSG_APPEND and int(st1["last_index"]) > int(st0["last_index"]) and not fl & abi.F_INVARIANT:
             first, last = int(st0["last_index"]) + 1, int(st1["last_index"])
@@ -180,7 +214,13 @@ class RaShell:
             tag = e if isinstance(e, str) else e[0]
             if tag == "exit":
                 raise RuntimeError(f"server {s}: the reference would exit with invariant {e[1]} on {m}")
-            if tag == "reply":
+            if tag == "reply" and kind == abi.MSG_TRANSFER_LEADERSHIP:
+                if call is not None:                                 # {reply, From, Reply}: to the caller
+                    call.reply = e[1]
+            elif tag == "send_msg" and e[2] == "election_timeout":  # {send_msg, Target, election_timeout, cast}
+                self.token += 1
+                self._post(peer(e[1]), fx.encode(peer(e[1]), fx.ElectionTimeout(self.token)))
+            elif tag == "reply":
                 to = peer(int(m["from"]))
                 self._post(to, fx.encode(to, e[1], from_slot=me))
             elif tag == "cast":
