@@ -18,6 +18,7 @@
          submit/3, submit/4, collect/1, start_collector/2, stop_collector/1, snapshot/2, wal_checksums/3,
          comm_unique_id/0, comm_init/4, allgather_leaderboard/2, node_leaderboard/3]).
 -export([wal_batch_checksums/2, wal_frame/4, wal_recover_check/2, wal_frame_batch/3, wal_recover/2]).
+-export([crc32s/3, crc32_stream/3, segment_build/5, segment_image/4]).
 -export([encode_msg/3, encode_msgs/1, decode_decision/1, decision_to_effects/3]).
 
 -include_lib("ra/src/ra.hrl").
@@ -135,6 +136,25 @@ wal_checksums(_Ctx, _EntriesBin, _DataBin) -> erlang:nif_error(not_loaded).
 
 wal_frame(_Ctx, _RecordsBin, _DataBin, _Flags) -> erlang:nif_error(not_loaded).
 wal_recover_check(_Ctx, _FileBin) -> erlang:nif_error(not_loaded).
+
+%% segments and snapshots: erlang:crc32/1,2 for a batch of entries, one long binary, a whole segment file
+crc32s(_Ctx, _EntriesBin, _DataBin) -> erlang:nif_error(not_loaded).
+crc32_stream(_Ctx, _Bin, _Init) -> erlang:nif_error(not_loaded).
+segment_build(_Ctx, _EntriesBin, _DataBin, _MaxCount, _Flags) -> erlang:nif_error(not_loaded).
+
+%% The bytes of a whole segment file for Entries = [{Idx, Term, Bin}] in the caller's order: what
+%% ra_log_segment:append/4 accumulates in pending_index / pending_data and flush/1 writes
+%% (src/ra_log_segment.erl:262-338); is_full/1 and the file I/O stay with the caller.
+segment_image(Ctx, Entries, MaxCount, ComputeChecksums) ->
+    {EntriesBin, Data, _} =
+        lists:foldl(fun({Idx, Term, Bin}, {E, D, Off}) ->
+                            Len = byte_size(Bin),
+                            {<<E/binary, Idx:64/little, Term:64/little, Off:64/little,
+                               Len:32/little, 0:32>>, [D, Bin], Off + Len}
+                    end, {<<>>, [], 0}, Entries),
+    Flags = case ComputeChecksums of true -> 0; false -> 1 end,
+    {ok, Image} = segment_build(Ctx, EntriesBin, iolist_to_binary(Data), MaxCount, Flags),
+    Image.
 
 %% ra_log_wal:write_data/8 computes erlang:adler32([<<Idx:64, Term:64>> | EntryData]) per record
 %% (src/ra_log_wal.erl:528-534); for a whole write_batch: Entries = [{Idx, Term, Bin}].

@@ -143,6 +143,91 @@ int rgb_wal_scan(const void *bytes, uint64_t n_bytes, rgb_wal_scanned *out, uint
 int rgb_wal_validate(rgb_ctx *ctx, const void *bytes, uint64_t n_bytes, const rgb_wal_scanned *recs,
                      uint32_t n, uint32_t *n_ok, uint32_t *status);
 
+/* ==== segments and snapshots: batched CRC-32 ===============================================
+ *
+ * Everything Ra writes behind the WAL is checksummed with erlang:crc32 -- zlib's CRC-32 (reflected
+ * polynomial 0xEDB88320, initial value and final xor 0xFFFFFFFF; the CRC of "123456789" is 0xCBF43926,
+ * of nothing 0):
+ *
+ *   - every entry a mem-table flush appends to a segment file (src/ra_log_segment.erl:277, compute_checksum
+ *     :1240-1243), validated again on every read (:670, validate_checksum :1245-1248);
+ *   - the segment file itself: <<"RASG", Version:16, MaxCount:16>> (:41-43, :1118-1122), MaxCount index
+ *     records <<Idx:64, Term:64, DataOffset:64, Length:32, Crc:32>> (version 2, 32 bytes; version 1 has a
+ *     32-bit DataOffset and 28 bytes, :44-45, :1197-1219), then the payloads back to back from
+ *     8 + MaxCount * 32 (data_start, :247);
+ *   - one CRC over a whole snapshot file, also chunk by chunk as erlang:crc32(Old, Chunk) while a
+ *     snapshot is received (src/ra_log_snapshot.erl:57, 81, 94, 107, 256; src/ra_snapshot.erl:1020, 1038).
+ *
+ * Device forms enqueue on `stream` (NULL = the context's stream) and do not synchronise; host-buffer forms
+ * stage through device buffers the context keeps and synchronise (PCIe-inclusive).  Only a payload's own
+ * bytes are read (16-byte pieces at the payload's own alignment), only the file's own bytes are written:
+ * no padding is needed around d_data or d_out, which may have any alignment.  The stream form keeps its
+ * partial values in a buffer of the context: one stream-form call per context at a time. */
+typedef struct rgb_seg_entry {
+  uint64_t index;        /* Idx  */
+  uint64_t term;         /* Term */
+  uint64_t data_offset;  /* payload = data[data_offset .. +data_len); from a scan: the absolute file offset */
+  uint32_t data_len;     /* Length */
+  uint32_t crc;          /* from a scan: the stored Crc; ignored on input */
+} rgb_seg_entry;
+
+#define RGB_SEG_NO_CHECKSUMS   1u   /* compute_checksums = false: Crc = 0 (src/ra_log_segment.erl:1240-1241) */
+#define RGB_SEG_VERSION        2u
+#define RGB_SEG_HEADER_BYTES   8u
+#define RGB_SEG_RECORD_BYTES   32u  /* version 2 */
+#define RGB_SEG_RECORD_BYTES_V1 28u
+
+/* d_crcs[i] = crc32(payload i) for the n entries of d_entries.  An entry whose payload does not lie inside
+ * [0, data_bytes) is skipped (its d_crcs slot is not written). */
+int rgb_crc32_device(rgb_ctx *ctx, const void *d_entries, uint32_t n, const void *d_data,
+                     uint64_t data_bytes, void *d_crcs, void *stream);
+/* Host-buffer form; a payload outside data_bytes is RGB_E_INVAL. */
+int rgb_crc32(rgb_ctx *ctx, const rgb_seg_entry *entries, uint32_t n, const void *data,
+              uint64_t data_bytes, uint32_t *crcs);
+
+/* *d_crc (one uint32_t in device memory) = erlang:crc32(init, Data) for one long buffer; init = 0 starts a
+ * new checksum, chaining calls over consecutive chunks gives the checksum of the whole. */
+int rgb_crc32_stream_device(rgb_ctx *ctx, const void *d_data, uint64_t n_bytes, uint32_t init,
+                            void *d_crc, void *stream);
+int rgb_crc32_stream(rgb_ctx *ctx, const void *data, uint64_t n_bytes, uint32_t init, uint32_t *crc_out);
+
+/* Host helper: out_offsets[i] = the absolute file offset of payload i (DataOffset) when the n payloads are
+ * written back to back, in the caller's order, behind MaxCount index records; returns the file size.
+ * out_offsets may be NULL. */
+uint64_t rgb_segment_layout(const rgb_seg_entry *entries, uint32_t n, uint32_t max_count,
+                            uint64_t *out_offsets);
+
+/* d_out[0 .. file size) = the segment file: header, n index records in the caller's order (the reference
+ * does not sort), zeros for the MaxCount - n unused records, the payload copies.  CRC and copy share the one
+ * read of each payload.  d_out_offsets = the n offsets rgb_segment_layout returned, in device memory.
+ * n > max_count, max_count > 65535, out_bytes below the index region or unknown flags: RGB_E_INVAL, nothing
+ * is enqueued.  Whether the segment is full (count or max_size) is the caller's decision.  An entry whose
+ * payload lies outside d_data, or whose copy would lie outside out_bytes, is skipped by the kernel. */
+int rgb_segment_build_device(rgb_ctx *ctx, const void *d_entries, uint32_t n, uint32_t max_count,
+                             const void *d_out_offsets, const void *d_data, uint64_t data_bytes,
+                             void *d_out, uint64_t out_bytes, uint32_t flags, void *stream);
+/* Host-buffer form: lays the file out itself; out_bytes below the file size or a payload outside data_bytes
+ * is RGB_E_INVAL and `out` is not written.  Bytes of `out` behind the file size are never written. */
+int rgb_segment_build(rgb_ctx *ctx, const rgb_seg_entry *entries, uint32_t n, uint32_t max_count,
+                      const void *data, uint64_t data_bytes, void *out, uint64_t out_bytes, uint32_t flags);
+
+#define RGB_SEG_END_ZEROS     0u   /* an all-zero index record: the end of the index (:1199-1201) */
+#define RGB_SEG_END_FULL      1u   /* MaxCount records read */
+#define RGB_SEG_END_TRUNCATED 2u   /* the file ends inside the index region, or record *n_out points behind
+                                      the end of the file: it is counted out, never read */
+#define RGB_SEG_END_CAP       3u   /* `cap` records stored, more follow */
+
+/* read_header/1 + the index walk (src/ra_log_segment.erl:1124-1138, 1197-1219) over the bytes of a whole
+ * segment file: unknown magic, fewer than 8 bytes, Version 0 or Version > 2 is RGB_E_INVAL.  out = NULL
+ * counts the records into *n_out.  Pure host code. */
+int rgb_segment_scan(const void *bytes, uint64_t n_bytes, rgb_seg_entry *out, uint32_t cap, uint32_t *n_out,
+                     uint32_t *version_out, uint32_t *max_count_out, uint32_t *end);
+
+/* validate_checksum/2 (:1245-1248) for the scanned records in order: a stored Crc of 0 means "not
+ * checked" and is always good.  *n_ok = the number of leading good records. */
+int rgb_segment_validate(rgb_ctx *ctx, const void *bytes, uint64_t n_bytes, const rgb_seg_entry *recs,
+                         uint32_t n, uint32_t *n_ok);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,13 @@ WAL_REC_FIRST, WAL_REC_VALIDATE, WAL_REC_UNKNOWN = 1, 2, 4
 WAL_END_ZEROS, WAL_END_DATA, WAL_END_CAP = 0, 1, 2
 WAL_CLEAN, WAL_DROPPED_LAST, WAL_CORRUPT = 0, 1, 2
 WAL_FILE_HEADER = b"RAWA\x01"
+# segments and snapshots (same header)
+SEG_ENTRY_DTYPE = np.dtype([("index", u64), ("term", u64), ("data_offset", u64), ("data_len", u32), ("crc", u32)])
+assert SEG_ENTRY_DTYPE.itemsize == 32
+SEG_NO_CHECKSUMS = 1
+SEG_VERSION, SEG_HEADER_BYTES, SEG_RECORD_BYTES, SEG_RECORD_BYTES_V1 = 2, 8, 32, 28
+SEG_END_ZEROS, SEG_END_FULL, SEG_END_TRUNCATED, SEG_END_CAP = 0, 1, 2, 3
+SEG_MAX_ENTRIES, SEG_MAX_SIZE_B = 4096, 64_000_000            # src/ra.hrl:225, 227
 
 # rgb_view (ABI v9, rgb_collect_view): pointers into the pinned slot the device wrote
 VIEW_DTYPE = np.dtype([("decisions", "<u8"), ("rpcs", "<u8"), ("tick", "<u8"), ("n", "<u4"), ("n_rpcs", "<u4"),

@@ -668,6 +668,53 @@ static ERL_NIF_TERM nif_wal_recover_check(ErlNifEnv *env, int argc, const ERL_NI
                           enif_make_uint(env, n_ok), enif_make_atom(env, st));
 }
 
+/* crc32s(Ctx, EntriesBin, DataBin) -> {ok, CrcsBin}: EntriesBin = n rgb_seg_entry records (index, term,
+ * data_offset, data_len, crc ignored), DataBin = the packed payload bytes; CrcsBin = n little-endian 32-bit
+ * values, erlang:crc32(Data) per entry (compute_checksum/2, src/ra_log_segment.erl:1240-1243) */
+static ERL_NIF_TERM nif_crc32s(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary e, d, out;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &e) ||
+      !enif_inspect_binary(env, argv[2], &d) || e.size % sizeof(rgb_seg_entry) != 0)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(e.size / sizeof(rgb_seg_entry));
+  if (!enif_alloc_binary((size_t)n * sizeof(uint32_t), &out)) return mk_error(env, c, RGB_E_NOMEM);
+  int rc = rgb_crc32(c->ctx, (const rgb_seg_entry *)e.data, n, d.data, d.size, (uint32_t *)out.data);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+}
+
+/* crc32_stream(Ctx, Bin, Init) -> {ok, Crc}: erlang:crc32(Init, Bin) of one long binary (a snapshot or a chunk
+ * of one: src/ra_log_snapshot.erl:57, 81, 94, 107, 256) */
+static ERL_NIF_TERM nif_crc32_stream(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary b; unsigned init; uint32_t crc = 0;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &b) || !enif_get_uint(env, argv[2], &init))
+    return enif_make_badarg(env);
+  int rc = rgb_crc32_stream(c->ctx, b.data, b.size, init, &crc);
+  if (rc) return mk_error(env, c, rc);
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_uint(env, crc));
+}
+
+/* segment_build(Ctx, EntriesBin, DataBin, MaxCount, Flags) -> {ok, SegmentBin}: the whole segment file of the
+ * n entries -- header, index records, zeros for the unused records, payloads -- what append/4 accumulates and
+ * flush/1 writes (src/ra_log_segment.erl:262-338, 1118-1122, 1211-1219).  Flags: 1 = compute_checksums false */
+static ERL_NIF_TERM nif_segment_build(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary e, d, out; unsigned max_count, flags;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &e) ||
+      !enif_inspect_binary(env, argv[2], &d) || !enif_get_uint(env, argv[3], &max_count) ||
+      !enif_get_uint(env, argv[4], &flags) || e.size % sizeof(rgb_seg_entry) != 0)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(e.size / sizeof(rgb_seg_entry));
+  if (n > max_count || max_count > 65535u) return mk_error(env, c, RGB_E_INVAL);
+  const uint64_t total = rgb_segment_layout((const rgb_seg_entry *)e.data, n, max_count, NULL);
+  if (!enif_alloc_binary((size_t)total, &out)) return mk_error(env, c, RGB_E_NOMEM);
+  int rc = rgb_segment_build(c->ctx, (const rgb_seg_entry *)e.data, n, max_count, d.data, d.size, out.data, total, flags);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+}
+
 static ErlNifFunc nif_funcs[] = {
   {"open", 4, nif_open, 0},
   {"register_groups", 3, nif_register_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
@@ -690,6 +737,9 @@ static ErlNifFunc nif_funcs[] = {
   {"wal_checksums", 3, nif_wal_checksums, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"wal_frame", 4, nif_wal_frame, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"wal_recover_check", 2, nif_wal_recover_check, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"crc32s", 3, nif_crc32s, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"crc32_stream", 3, nif_crc32_stream, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_build", 5, nif_segment_build, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(ra_gpu_batch, nif_funcs, on_load, NULL, NULL, NULL)

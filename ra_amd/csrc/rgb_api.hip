@@ -214,6 +214,7 @@ static int launch_tick_classes(rgb_ctx *ctx, const rgb_dev &dev, const rgb_msg *
 }
 
 extern "C" void rgb_wal_release(rgb_ctx *ctx);   /* rgb_wal.hip: staging buffers of the host-buffer form */
+extern "C" void rgb_seg_release(rgb_ctx *ctx);   /* rgb_segment.hip: the same for the segment / snapshot part */
 
 extern "C" {
 
@@ -311,6 +312,7 @@ void rgb_close(rgb_ctx *ctx) {
   if (!ctx) return;
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   rgb_wal_release(ctx);
+  rgb_seg_release(ctx);
   for (u32 k = 0; k < ctx->ring_size; ++k) free_slot(ctx->ring_mem[k]);
   if (ctx->dev.dbg_buf) (void)hipFree(ctx->dev.dbg_buf);
   if (ctx->dev.hot) (void)hipFree(ctx->dev.hot);

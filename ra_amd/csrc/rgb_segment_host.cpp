@@ -1,0 +1,59 @@
+/*
+ * rgb_segment_host.cpp -- the host-only half of the segment part of include/ra_gpu_wal.h: the file layout and the
+ * index walk of a segment file (src/ra_log_segment.erl:1118-1138, 1197-1219).  No HIP here, so the file also builds
+ * on its own under the sanitizers (tests/test_segment.py::test_segment_scan_under_sanitizers).
+ */
+#include <stdint.h>
+#include "../../include/ra_gpu_wal.h"
+
+extern "C" uint64_t rgb_segment_layout(const rgb_seg_entry *entries, uint32_t n, uint32_t max_count,
+                                       uint64_t *out_offsets) {
+  uint64_t pos = (uint64_t)RGB_SEG_HEADER_BYTES + (uint64_t)RGB_SEG_RECORD_BYTES * max_count;   /* data_start, :247 */
+  for (uint32_t i = 0; i < n; ++i) {
+    if (out_offsets) out_offsets[i] = pos;
+    pos += entries[i].data_len;                                   /* data_offset = DataOffset + Length, :277 */
+  }
+  return pos;
+}
+
+namespace {
+inline uint64_t seg_be(const unsigned char *p, int nbytes) {
+  uint64_t v = 0;
+  for (int k = 0; k < nbytes; ++k) v = (v << 8) | p[k];
+  return v;
+}
+}  // namespace
+
+extern "C" int rgb_segment_scan(const void *bytes, uint64_t n_bytes, rgb_seg_entry *out, uint32_t cap,
+                                uint32_t *n_out, uint32_t *version_out, uint32_t *max_count_out, uint32_t *end) {
+  if (!bytes || !n_out || !version_out || !max_count_out || !end) return RGB_E_INVAL;
+  const unsigned char *b = (const unsigned char *)bytes;
+  /* <<"RASG", Version:16, MaxCount:16>> when Version =< 2 (:1124-1133); formats exist for 1 and 2 (:1180-1189) */
+  if (n_bytes < RGB_SEG_HEADER_BYTES || b[0] != 'R' || b[1] != 'A' || b[2] != 'S' || b[3] != 'G') return RGB_E_INVAL;
+  const uint32_t version = (uint32_t)seg_be(b + 4, 2), max_count = (uint32_t)seg_be(b + 6, 2);
+  if (version < 1u || version > RGB_SEG_VERSION) return RGB_E_INVAL;
+  *version_out = version;
+  *max_count_out = max_count;
+  const uint32_t rec = version == 2u ? RGB_SEG_RECORD_BYTES : RGB_SEG_RECORD_BYTES_V1;
+  const int off_bytes = version == 2u ? 8 : 4;
+  const bool count_only = out == nullptr;
+  uint32_t n = 0;
+  *end = RGB_SEG_END_FULL;
+  for (uint32_t k = 0; k < max_count; ++k) {
+    const uint64_t pos = (uint64_t)RGB_SEG_HEADER_BYTES + (uint64_t)rec * k;
+    if (pos + rec > n_bytes) { *end = RGB_SEG_END_TRUNCATED; break; }       /* decode_index_record/3's last clause */
+    const unsigned char *p = b + pos;
+    const uint64_t idx = seg_be(p, 8), term = seg_be(p + 8, 8), data_off = seg_be(p + 16, off_bytes);
+    const uint32_t len = (uint32_t)seg_be(p + 16 + off_bytes, 4), crc = (uint32_t)seg_be(p + 20 + off_bytes, 4);
+    if (idx == 0 && term == 0 && data_off == 0 && len == 0 && crc == 0) { *end = RGB_SEG_END_ZEROS; break; }
+    if (data_off > n_bytes || len > n_bytes - data_off) { *end = RGB_SEG_END_TRUNCATED; break; }
+    if (!count_only) {
+      if (n == cap) { *end = RGB_SEG_END_CAP; break; }
+      rgb_seg_entry &r = out[n];
+      r.index = idx; r.term = term; r.data_offset = data_off; r.data_len = len; r.crc = crc;
+    }
+    n += 1;
+  }
+  *n_out = n;
+  return RGB_OK;
+}

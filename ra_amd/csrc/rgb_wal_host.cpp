@@ -85,3 +85,9 @@ extern "C" int rgb_wal_scan(const void *bytes, uint64_t n_bytes, rgb_wal_scanned
   return RGB_OK;
 }
 
+
+/* the emulated library (tests/native) builds the WAL sources as one unit: the segment part rides along */
+#ifdef RGB_HOST_EMULATION
+#include "rgb_segment.hip"
+#include "rgb_segment_host.cpp"
+#endif

@@ -42,7 +42,9 @@ OPTIONAL_IN_OLD_BUILDS = {"rgb_synth_tick_stamped_device", "rgb_synth_stamps_res
                           "rgb_train_plan_download", "rgb_train_plan_fit", "rgb_submit_seq", "rgb_set_seq_ranges_device",
                           "rgb_collect_view", "rgb_release"} | set(COMM_EXPORTS)
 WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "rgb_wal_frame_device",
-               "rgb_wal_frame", "rgb_wal_scan", "rgb_wal_validate"]                            # include/ra_gpu_wal.h
+               "rgb_wal_frame", "rgb_wal_scan", "rgb_wal_validate",
+               "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
+               "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate"]                            # include/ra_gpu_wal.h
 
 
 class RgbError(RuntimeError):
@@ -53,7 +55,8 @@ class RgbError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("rgb_kernels.hip", "rgb_api.hip", "rgb_wal.hip", "rgb_wal_host.cpp", "rgb_comm.cpp", "rgb_internal.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("rgb_kernels.hip", "rgb_api.hip", "rgb_wal.hip", "rgb_wal_host.cpp", "rgb_segment.hip",
+                                              "rgb_segment_host.cpp", "rgb_comm.cpp", "rgb_internal.h")]
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "ra_gpu_wal.h"))
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "ra_gpu_batch.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
@@ -185,6 +188,17 @@ def lib():
     L.rgb_wal_frame.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64, u32]
     L.rgb_wal_scan.argtypes = [vp, C.c_uint64, vp, u32, C.POINTER(C.c_uint32), u64p, C.POINTER(C.c_uint32)]
     L.rgb_wal_validate.argtypes = [vp, vp, C.c_uint64, vp, u32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    u32p = C.POINTER(C.c_uint32)
+    L.rgb_crc32_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp]
+    L.rgb_crc32.argtypes = [vp, vp, u32, vp, C.c_uint64, vp]
+    L.rgb_crc32_stream_device.argtypes = [vp, vp, C.c_uint64, u32, vp, vp]
+    L.rgb_crc32_stream.argtypes = [vp, vp, C.c_uint64, u32, u32p]
+    L.rgb_segment_layout.restype = C.c_uint64
+    L.rgb_segment_layout.argtypes = [vp, u32, u32, vp]
+    L.rgb_segment_build_device.argtypes = [vp, vp, u32, u32, vp, vp, C.c_uint64, vp, C.c_uint64, u32, vp]
+    L.rgb_segment_build.argtypes = [vp, vp, u32, u32, vp, C.c_uint64, vp, C.c_uint64, u32]
+    L.rgb_segment_scan.argtypes = [vp, C.c_uint64, vp, u32, u32p, u32p, u32p, u32p]
+    L.rgb_segment_validate.argtypes = [vp, vp, C.c_uint64, vp, u32, u32p]
     if L.rgb_abi_version() != abi.ABI_VERSION and not (os.environ.get("RGB_LIB") and L.rgb_abi_version() == abi.ABI_VERSION - 1):
         raise RuntimeError("ABI version mismatch")     # (RGB_LIB=<the previous ABI's build>: A/B timing, tools/ only)
     for i, dt in enumerate(abi.STRUCT_DTYPES):
@@ -513,6 +527,68 @@ class RaGpuBatch:
                                              C.byref(n_ok), C.byref(status)), "rgb_wal_validate")
         return n_ok.value, status.value
 
+    # -- segments and snapshots: batched CRC-32 (include/ra_gpu_wal.h) ------------------
+    def crc32_device(self, d_entries: int, n: int, d_data: int, data_bytes: int, d_crcs: int, stream: int = 0):
+        """erlang:crc32(Payload) of n rgb_seg_entry records whose payloads are resident in device memory
+        (src/ra_log_segment.erl:277, 670, 1240-1248); enqueues and returns."""
+        self._check(self._L.rgb_crc32_device(self._h, d_entries, n, d_data, data_bytes, d_crcs, stream or None),
+                    "rgb_crc32_device")
+
+    def crc32(self, entries: np.ndarray, data: np.ndarray) -> np.ndarray:
+        """Host-buffer form: CRC-32 of `entries` (abi.SEG_ENTRY_DTYPE) over the packed payload bytes."""
+        entries = np.ascontiguousarray(entries, dtype=abi.SEG_ENTRY_DTYPE)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        out = np.zeros(len(entries), dtype=np.uint32)
+        self._check(self._L.rgb_crc32(self._h, entries.ctypes.data, len(entries),
+                                      data.ctypes.data if len(data) else None, len(data), out.ctypes.data), "rgb_crc32")
+        return out
+
+    def crc32_stream_device(self, d_data: int, n_bytes: int, init: int, d_crc: int, stream: int = 0):
+        """*d_crc = erlang:crc32(init, Data) of one long device buffer (src/ra_log_snapshot.erl:57-107); enqueues."""
+        self._check(self._L.rgb_crc32_stream_device(self._h, d_data or None, n_bytes, init, d_crc, stream or None),
+                    "rgb_crc32_stream_device")
+
+    def crc32_stream(self, data, init: int = 0) -> int:
+        """Host-buffer form of crc32_stream_device: zlib.crc32(data, init)."""
+        data = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else \
+            np.ascontiguousarray(data, dtype=np.uint8)
+        out = C.c_uint32(0)
+        self._check(self._L.rgb_crc32_stream(self._h, data.ctypes.data if len(data) else None, len(data), init,
+                                             C.byref(out)), "rgb_crc32_stream")
+        return out.value
+
+    def segment_build_device(self, d_entries: int, n: int, max_count: int, d_out_offsets: int, d_data: int,
+                             data_bytes: int, d_out: int, out_bytes: int, flags: int = 0, stream: int = 0):
+        """The whole segment file image of n entries into d_out (src/ra_log_segment.erl:1118-1122, 1211-1219):
+        header, index records, zeros for the unused records, payload copies; enqueues and returns."""
+        self._check(self._L.rgb_segment_build_device(self._h, d_entries or None, n, max_count, d_out_offsets or None,
+                                                     d_data or None, data_bytes, d_out, out_bytes, flags,
+                                                     stream or None), "rgb_segment_build_device")
+
+    def segment_build(self, entries: np.ndarray, data: np.ndarray, max_count: int = 4096, flags: int = 0,
+                      out: np.ndarray | None = None) -> np.ndarray:
+        """Host-buffer form: the file bytes of `entries` (abi.SEG_ENTRY_DTYPE).  `out` (uint8, at least the file
+        size) is filled in place when given; bytes behind the file size are left alone."""
+        entries = np.ascontiguousarray(entries, dtype=abi.SEG_ENTRY_DTYPE)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if out is None:
+            out = np.zeros(segment_layout(entries, max_count)[1], dtype=np.uint8)
+        self._check(self._L.rgb_segment_build(self._h, entries.ctypes.data if len(entries) else None, len(entries),
+                                              max_count, data.ctypes.data if len(data) else None, len(data),
+                                              out.ctypes.data, len(out), flags), "rgb_segment_build")
+        return out
+
+    def segment_validate(self, file_bytes: np.ndarray, recs: np.ndarray) -> int:
+        """Number of leading records of a scanned segment whose payload matches the stored CRC (0 = not checked,
+        src/ra_log_segment.erl:1245-1248)."""
+        file_bytes = np.ascontiguousarray(file_bytes, dtype=np.uint8)
+        recs = np.ascontiguousarray(recs, dtype=abi.SEG_ENTRY_DTYPE)
+        n_ok = C.c_uint32(0)
+        self._check(self._L.rgb_segment_validate(self._h, file_bytes.ctypes.data if len(file_bytes) else None,
+                                                 len(file_bytes), recs.ctypes.data if len(recs) else None, len(recs),
+                                                 C.byref(n_ok)), "rgb_segment_validate")
+        return n_ok.value
+
     # -- observability -----------------------------------------------------------------
     def snapshot(self) -> np.ndarray:
         rows = np.zeros(self.n_groups, dtype=abi.LEADERBOARD_DTYPE)
@@ -663,6 +739,35 @@ def wal_scan(file_bytes, cap: int | None = None):
     if rc != 0:
         raise RgbError(rc, "rgb_wal_scan")
     return out[:n.value].copy(), consumed.value, end.value
+
+
+def segment_layout(entries: np.ndarray, max_count: int = 4096):
+    """(DataOffset of every payload, file size) of a segment with MaxCount index records (host helper)."""
+    entries = np.ascontiguousarray(entries, dtype=abi.SEG_ENTRY_DTYPE)
+    offs = np.zeros(len(entries), dtype=np.uint64)
+    size = lib().rgb_segment_layout(entries.ctypes.data if len(entries) else None, len(entries), max_count,
+                                    offs.ctypes.data if len(entries) else None)
+    return offs, int(size)
+
+
+def segment_scan(file_bytes, cap: int | None = None):
+    """read_header/1 and the index walk over a whole segment file (host code, no device):
+    (records as abi.SEG_ENTRY_DTYPE, version, max_count, end reason abi.SEG_END_*)."""
+    buf = np.frombuffer(bytes(file_bytes), dtype=np.uint8) if not isinstance(file_bytes, np.ndarray) else \
+        np.ascontiguousarray(file_bytes, dtype=np.uint8)
+    n, ver, mc, end = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    ptr = buf.ctypes.data if len(buf) else None
+    if cap is None:
+        rc = lib().rgb_segment_scan(ptr, len(buf), None, 0, C.byref(n), C.byref(ver), C.byref(mc), C.byref(end))
+        if rc != 0:
+            raise RgbError(rc, "rgb_segment_scan")
+        cap = max(1, n.value)
+    out = np.zeros(cap, dtype=abi.SEG_ENTRY_DTYPE)
+    rc = lib().rgb_segment_scan(ptr, len(buf), out.ctypes.data, cap, C.byref(n), C.byref(ver), C.byref(mc),
+                                C.byref(end))
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_scan")
+    return out[:n.value].copy(), ver.value, mc.value, end.value
 
 
 def combine_checksums(per_server: np.ndarray, first: int = 0) -> int:
