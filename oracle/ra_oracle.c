@@ -998,6 +998,15 @@ static int follower_snapshot_written(oserver *sv, const rgb_msg *m, ofx *fx) {
   return 0;
 }
 
+/* the reply of a call: RGB_F_CALL_REPLY, the code RGB_CALL_* in reply_next_index; reply_to names the target of the
+ * {send_msg, Target, election_timeout, cast} that goes with `ok` and is RGB_NONE with every error reply */
+static void call_reply(uint64_t code, uint8_t send_to, ofx *fx) {
+  fx->has_reply = 1;
+  fx->flags |= RGB_F_CALL_REPLY;
+  fx->r_term = 0; fx->r_next = code; fx->r_last = 0; fx->r_lterm = 0;
+  fx->reply_to = send_to;
+}
+
 static int handle_follower(oserver *sv, const rgb_msg *m, ofx *fx) {
   switch (m->kind) {
     case RGB_MSG_SNAPSHOT_WRITTEN: return follower_snapshot_written(sv, m, fx);
@@ -1030,10 +1039,40 @@ static int handle_follower(oserver *sv, const rgb_msg *m, ofx *fx) {
       if (sv->s.self_nonvoter) return 0;                   /* :1619-1624 */
       call_for_election_pre_vote(sv, m->c, fx);            /* :1625-1626 */
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP:                      /* :1655-1657 {call, From}: unsupported_call */
+      call_reply(RGB_CALL_UNSUPPORTED, RGB_NONE, fx);
+      return 0;
     default:
       fx->flags |= RGB_F_UNHANDLED;                        /* :1655 catch-all */
       return 0;
   }
+}
+
+/* handle_leader({transfer_leadership, Target}, State), src/ra_server.erl:996-1035, clause by clause */
+static void leader_transfer_leadership(oserver *sv, const rgb_msg *m, ofx *fx) {
+  oscal *s = &sv->s;
+  const unsigned target = m->from;
+  if (target == s->self) {                                  /* :996-1000 cfg.id = Target */
+    call_reply(RGB_CALL_ALREADY_LEADER, RGB_NONE, fx);
+    return;
+  }
+  if (!is_present(s, target)) {                             /* :1001-1007 not is_map_key(Member, Members) */
+    call_reply(RGB_CALL_UNKNOWN_MEMBER, RGB_NONE, fx);
+    return;
+  }
+  if (!((s->voter_mask >> target) & 1u)) {                  /* :1012-1017 membership =/= voter */
+    call_reply(RGB_CALL_NON_VOTER, RGB_NONE, fx);
+    return;
+  }
+  if (s->next_index[target] != log_next_index(&sv->log)) {  /* :1018-1020, 1030-1033 */
+    call_reply(RGB_CALL_NOT_UP_TO_DATE, RGB_NONE, fx);
+    return;
+  }
+  /* :1020-1029 [{reply, ok}, {send_msg, Target, election_timeout, cast}]; the condition carries
+   * transfer_leadership_condition/2 and timeout => #{effects => [], transition_to => leader} */
+  call_reply(RGB_CALL_OK, (uint8_t)target, fx);
+  set_role(s, RGB_ROLE_AWAIT_CONDITION, fx);
+  s->cond_reason = RGB_COND_TRANSFER_LEADERSHIP;
 }
 
 /* --------------------------------------------------------------- leader clauses -- */
@@ -1188,6 +1227,9 @@ static int handle_leader(struct ora_ctx *c, oserver *sv, uint32_t srv_id, const 
     case RGB_MSG_SNAPSHOT_WRITTEN:                         /* :745-747 other ra_log_events */
       log_snapshot_written(l, m->a, m->b);
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP:                      /* :996-1035 */
+      leader_transfer_leadership(sv, m, fx);
+      return 0;
     default:
       fx->flags |= RGB_F_UNHANDLED;
       return 0;
@@ -1274,6 +1316,9 @@ static int handle_candidate(oserver *sv, const rgb_msg *m, ofx *fx, int *reproce
     case RGB_MSG_ELECTION_TIMEOUT:
       call_for_election_candidate(sv, fx);                  /* :1161-1162 */
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP:                       /* :1186-1188 {call, From}: unsupported_call */
+      call_reply(RGB_CALL_UNSUPPORTED, RGB_NONE, fx);
+      return 0;
     default:
       fx->flags |= RGB_F_UNHANDLED;
       return 0;
@@ -1352,6 +1397,9 @@ static int handle_pre_vote(oserver *sv, const rgb_msg *m, ofx *fx, int *reproces
     case RGB_MSG_ELECTION_TIMEOUT:
       call_for_election_pre_vote(sv, m->c, fx);             /* :1255-1256 */
       return 0;
+    case RGB_MSG_TRANSFER_LEADERSHIP:                       /* :1276-1278 {call, From}: unsupported_call */
+      call_reply(RGB_CALL_UNSUPPORTED, RGB_NONE, fx);
+      return 0;
     default:
       fx->flags |= RGB_F_UNHANDLED;
       return 0;
@@ -1394,6 +1442,12 @@ static int handle_await_condition(oserver *sv, const rgb_msg *m, ofx *fx, int *r
       *reprocess = 1;
       return 0;
     case RGB_MSG_AWAIT_TIMEOUT: {
+      if (s->cond_reason == RGB_COND_TRANSFER_LEADERSHIP) {
+        /* :1932-1945 with transfer_leadership_condition(_Msg, _) -> false :2243-2244 and the timeout map of
+         * :1027-1028: #{effects => [], transition_to => leader} */
+        set_role(s, RGB_ROLE_LEADER, fx);
+        return 0;
+      }
       /* :1932-1945; follower_catchup_cond(_, _Msg, _) -> false :2229-2230: replay the stored
        * effects [cast reply, record_leader_msg] and return to follower */
       fx->has_reply = 1;
@@ -1416,9 +1470,12 @@ static int handle_await_condition(oserver *sv, const rgb_msg *m, ofx *fx, int *r
       call_for_election_pre_vote(sv, m->c, fx);             /* :1930-1931 */
       return 0;
     case RGB_MSG_AER: {
-      /* follower_catchup_cond/3 :2201-2218 */
       int pred = 0;
-      if (m->term >= s->current_term) {
+      if (s->cond_reason == RGB_COND_TRANSFER_LEADERSHIP) {
+        /* transfer_leadership_condition/2 :2235-2238: Term > CurTerm; the condition map has no top-level
+         * transition_to, so :1953 releases to follower */
+        pred = m->term > s->current_term;
+      } else if (m->term >= s->current_term) {              /* follower_catchup_cond/3 :2201-2218 */
         int h = has_log_entry_or_snapshot(&sv->log, m->a, m->b);
         if (h == HLE_OK) pred = 1;
         else if (h == HLE_MISMATCH) pred = (s->cond_reason == RGB_COND_MISSING);
@@ -1573,6 +1630,8 @@ uint32_t ora_n_servers(const ora_ctx *c) { return c->n_servers; }
 
 int ora_set_state(ora_ctx *c, uint32_t first, uint32_t n, const rgb_server_state *in) {
   if ((uint64_t)first + n > c->n_servers) return RGB_E_INVAL;
+  for (uint32_t k = 0; k < n; k++)                         /* as the library's upload: refused as a whole */
+    if (in[k].cond_reason > RGB_COND_TRANSFER_LEADERSHIP) return RGB_E_INVAL;
   for (uint32_t k = 0; k < n; k++) {
     const rgb_server_state *h = &in[k];
     oserver *sv = &c->sv[first + k];
@@ -1699,6 +1758,12 @@ int ora_get_state(const ora_ctx *c, uint32_t first, uint32_t n, rgb_server_state
       }
       h->n_runs = (uint8_t)nr;
       if (overflow) return RGB_E_UNSUPPORTED;
+    } else if (l->snap_idx == UNDEF) {
+      /* neither a range nor a snapshot (ra_log:next_index/1 = 0, src/ra_log.erl:1173-1174): last_index_term/1 is
+       * `undefined`, a form the boundary has no spelling for -- such a log only ever comes from an upload, and the
+       * cursors go back as they came, as the library hands them back */
+      h->first_index = l->first; h->last_index = l->last; h->last_term = l->last_term;
+      h->n_runs = 0;
     } else {
       h->first_index = h->last_index + 1;
       h->n_runs = 0;

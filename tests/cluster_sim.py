@@ -22,7 +22,12 @@ gen_statem would route the reference's effects:
 The network between members drops and delays, and reorders between different senders (never between
 the same two members, never duplicating: Erlang distribution); local events (WAL, next_event) are
 reliable and ordered.  Timers (election_timeout, await_condition_timeout) and client commands
-fire at random.  With p_wal_down > 0 a member's WAL goes down for a few ticks now and then: a follower's
+fire at random.  With p_transfer > 0 a client now and then calls the leader with {transfer_leadership, Target} (a random
+member, the leader itself or a stranger): `ok` comes with {send_msg, Target, election_timeout, cast}, routed to the target
+as an election timeout with a fresh token, while the old leader waits in await_condition (RGB_COND_TRANSFER_LEADERSHIP)
+until an append_entries_rpc of a higher term releases it or await_condition_timeout makes it leader again; the
+transfer_leadership hint of a leader's wal_down timeout (RGB_F_TRANSFER_LEADERSHIP) is then posted to the server itself
+as that call.  With p_wal_down > 0 a member's WAL goes down for a few ticks now and then: a follower's
 ra_log:write/2 then answers {error, wal_down} and a leader's ra_log:append/2 raises wal_down -- host I/O, so the host
 recipes of INTEGRATION.md put the server into await_condition (RGB_COND_WAL_DOWN / RGB_COND_WAL_DOWN_LEADER) and
 RGB_MF_CAN_WRITE says when ra_log:can_write/1 is true again.  With p_snapshot > 0 members also take snapshots (SNAPSHOT_WRITTEN truncates their logs) and a
@@ -41,7 +46,7 @@ from ra_amd import abi, effects
 class ClusterSim:
     def __init__(self, eng, n_groups, n_members, seed, drop=0.1, max_delay=3,
                  p_election=0.02, p_command=0.3, p_query=0.05, p_tick=0.3, max_leaders=9, p_snapshot=0.0,
-                 p_wal_down=0.0):
+                 p_wal_down=0.0, p_transfer=0.0):
         self.eng, self.G, self.N = eng, n_groups, n_members
         self.S = n_groups * n_members
         self.rng = np.random.default_rng(seed)
@@ -51,6 +56,9 @@ class ClusterSim:
         self.p_snapshot = p_snapshot                     # > 0: members take snapshots at last_applied
         self.p_wal_down = p_wal_down                     # > 0: per member and tick, its WAL goes down for 2..7 ticks
         self.wal_injection = p_wal_down > 0              # (stays set after heal(): RGB_MF_CAN_WRITE keeps being passed)
+        self.p_transfer = p_transfer                     # > 0: per idle leader and tick, a client calls transfer_leadership
+        self.transfers = []                              # accepted and not yet judged: [group, target, term, next term seen]
+        self.transfer_codes = set()                      # RGB_CALL_* replies seen
         self.wal_up_at = np.zeros(self.S, dtype=np.int64)   # first tick at which ra_log:can_write/1 is true again
         self.host = []                                   # host-level snapshot transfers: (deliver_at, what, args)
         self.tick = 0
@@ -63,7 +71,8 @@ class ClusterSim:
         self.elections = np.zeros(n_groups, dtype=np.int64)
         self.stats = {"msgs": 0, "dropped": 0, "invariants": 0, "commands": 0, "queries_answered": 0,
                       "snapshots": 0, "installs": 0, "install_refused": 0,
-                      "wal_down_follower": 0, "wal_down_leader": 0, "transfer_leadership": 0, "wal_down_reprocessed": 0}
+                      "wal_down_follower": 0, "wal_down_leader": 0, "transfer_leadership": 0, "wal_down_reprocessed": 0,
+                      "transfer_ok": 0, "transfer_refused": 0, "transfer_completed": 0, "transfer_timed_out": 0}
         self.history = []                                # the batches fed to the engine, for replay
         self.leader_contact = np.full(self.S, -10**9, dtype=np.int64)   # tick of the last {record_leader_msg, _}
         self.election_silence = 0                        # ticks without a leader message before a timeout may fire
@@ -121,6 +130,14 @@ class ClusterSim:
                 self.stats["snapshots"] += 1
                 return effects.encode(s, effects.SnapshotWritten(la, term))
         if role == abi.ROLE_LEADER:
+            if self.p_transfer and self.elections[g] < self.max_leaders and self.rng.random() < self.p_transfer:
+                # ra:transfer_leadership(Leader, Target): mostly another member, now and then the leader itself, a
+                # slot beyond the group or a server id that is no member at all (within the group's election budget:
+                # every hand-over is a new term, one more run in every member's run table)
+                others = [j for j in range(self.N) if j != s % self.N]
+                pick = [s % self.N, min(self.N, 7), None] + others * 4
+                target = pick[int(self.rng.integers(0, len(pick)))]
+                return effects.encode(s, effects.TransferLeadership(target))
             if self.rng.random() < self.p_command:
                 self.stats["commands"] += 1
                 return effects.encode(s, effects.Commands(int(self.rng.integers(1, 4))))
@@ -170,8 +187,26 @@ class ClusterSim:
             by_msg.setdefault(int(r["msg_index"]), []).append(r)
         for i, (m, d) in enumerate(zip(msgs, dec)):
             self.route(m, d, by_msg.get(i, []), before[int(m["server"])], after[int(m["server"])])
+        self.judge_transfers()
         self.flush_wals()
         return msgs, dec, rpcs
+
+    def judge_transfers(self):
+        """An accepted transfer is COMPLETED when the leader of the next term the group reaches is the target."""
+        for tr in list(self.transfers):
+            g, target, term, nxt = tr
+            rows = self.state[g * self.N:(g + 1) * self.N]
+            above = [int(r["current_term"]) for r in rows if int(r["current_term"]) > term]
+            if not above:
+                continue
+            if nxt is None:
+                tr[3] = nxt = min(above)
+            led = [i for i, r in enumerate(rows) if int(r["role"]) == abi.ROLE_LEADER and int(r["current_term"]) == nxt]
+            if led:
+                self.stats["transfer_completed"] += int(led == [target])
+                self.transfers.remove(tr)
+            elif max(above) > nxt:
+                self.transfers.remove(tr)                # the group moved on: that term had no leader we saw
 
     # ------------------------------------------------------------------ effects -> messages
     def route(self, m, d, rpcs, st0, st1):
@@ -183,6 +218,21 @@ class ClusterSim:
             # {next_event, cast, {transfer_leadership, Peer}}: ra_server's own clause (not on the batched path); a
             # leader that declines the hint simply goes on leading, which is what happens here
             self.stats["transfer_leadership"] += 1
+            if self.p_transfer:
+                # .. unless transfers are on: the cast reaches handle_leader/2 with PeerId = hd(maps:to_list(
+                # maps:remove(Self, Cluster))), the lowest other member (src/ra_server.erl:660-668)
+                others = [j for j in range(self.N) if j != me and (int(st1["present_mask"]) >> j) & 1]
+                self.local[s].append(effects.encode(s, effects.TransferLeadership(others[0])))
+        if kind == abi.MSG_AWAIT_TIMEOUT and int(st0["role"]) == abi.ROLE_AWAIT_CONDITION and \
+                int(st0["cond_reason"]) == abi.COND_TRANSFER_LEADERSHIP:
+            assert int(st1["role"]) == abi.ROLE_LEADER and fl == abi.F_ROLE_CHANGED, (s, hex(fl))   # :1027-1028
+            self.stats["transfer_timed_out"] += 1
+        if fl & abi.F_CALL_REPLY:
+            code = int(d["reply_next_index"])
+            self.transfer_codes.add(code)
+            self.stats["transfer_ok" if code == abi.CALL_OK else "transfer_refused"] += 1
+            if code == abi.CALL_OK:
+                self.transfers.append([g, int(d["reply_to"]), int(st0["current_term"]), None])
         if int(st0["role"]) == abi.ROLE_AWAIT_CONDITION and int(st0["cond_reason"]) in (abi.COND_WAL_DOWN, abi.COND_WAL_DOWN_LEADER) \
                 and fl & abi.F_REPROCESSED:
             self.stats["wal_down_reprocessed"] += 1
@@ -217,6 +267,11 @@ class ClusterSim:
                 self.stats["invariants"] += 1
                 raise AssertionError(f"tick {self.tick}: server {s} hit reference invariant {e[1]} "
                                      f"on {m} in state {st0}")
+            elif tag == "reply" and kind == abi.MSG_TRANSFER_LEADERSHIP:
+                pass                                                 # {reply, From, Reply}: to the client, counted above
+            elif tag == "send_msg" and e[2] == "election_timeout":  # {send_msg, Target, election_timeout, cast}
+                self.token += 1
+                self.send(peer(e[1]), effects.encode(peer(e[1]), effects.ElectionTimeout(self.token)))
             elif tag == "reply":                                     # {reply, _}: back to the caller
                 to = int(m["from"])
                 self.send(peer(to), effects.encode(peer(to), e[1], from_slot=me))

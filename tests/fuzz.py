@@ -11,8 +11,20 @@ import numpy as np
 from ra_amd import abi
 
 
+def ra_log_next_index(row) -> int:
+    """ra_log:next_index/1 (src/ra_log.erl:1166-1174): range, else snapshot + 1, else 0."""
+    if int(row["first_index"]) <= int(row["last_index"]):
+        return int(row["last_index"]) + 1
+    if int(row["snapshot_index"]) != abi.UNDEF_INT:
+        return int(row["snapshot_index"]) + 1
+    return 0
+
+
 def random_states(rng: np.random.Generator, n_groups: int, n_members: int, max_runs: int = 8,
-                  backlog: int = 24) -> np.ndarray:
+                  backlog: int = 24, transfers: float = 0.0) -> np.ndarray:
+    """transfers (opt-in; 0 draws nothing more, so every existing seed keeps its stream): that share of the leaders
+    gets a peer level with ra_log:next_index/1 (the one {transfer_leadership, Peer} is accepted for) and that share
+    of the servers in await_condition awaits RGB_COND_TRANSFER_LEADERSHIP."""
     S = n_groups * n_members
     st = abi.empty_server_states(n_groups, n_members)
     for s in range(S):
@@ -97,6 +109,13 @@ def random_states(rng: np.random.Generator, n_groups: int, n_members: int, max_r
             st["match_index"][s, j] = mi
             st["next_index"][s, j] = ni
             st["commit_index_sent"][s, j] = max(0, int(st["commit_index"][s]) - int(rng.integers(0, 3)))
+    if transfers > 0.0:
+        for s in range(S):
+            role = int(st["role"][s])
+            if role == abi.ROLE_LEADER and rng.random() < transfers:
+                st["next_index"][s, int(rng.integers(0, n_members))] = ra_log_next_index(st[s])
+            elif role == abi.ROLE_AWAIT_CONDITION and rng.random() < transfers:
+                st["cond_reason"][s] = abi.COND_TRANSFER_LEADERSHIP
     return st
 
 
@@ -109,8 +128,13 @@ def _term_at(row, idx):
     return None
 
 
-def random_msgs(rng: np.random.Generator, st: np.ndarray, n_members: int, frac: float = 0.9) -> np.ndarray:
-    """At most one message per server (a tick), for a random `frac` of the servers, shuffled."""
+def random_msgs(rng: np.random.Generator, st: np.ndarray, n_members: int, frac: float = 0.9,
+                transfers: float = 0.0) -> np.ndarray:
+    """At most one message per server (a tick), for a random `frac` of the servers, shuffled.
+    transfers (opt-in; 0 draws nothing more): that share of the messages becomes the call {transfer_leadership, Target}
+    with Target drawn from self, the peers level with ra_log:next_index/1, the other members, a slot beyond the group
+    and RGB_NONE; a server that awaits RGB_COND_TRANSFER_LEADERSHIP gets a raised share of the two messages that end
+    the wait, an append_entries_rpc of a higher term and await_condition_timeout."""
     S = len(st)
     targets = np.flatnonzero(rng.random(S) < frac)
     rng.shuffle(targets)
@@ -237,7 +261,31 @@ def random_msgs(rng: np.random.Generator, st: np.ndarray, n_members: int, frac: 
         elif kind == abi.MSG_PIPELINE_RPCS:
             m["flags"][q] = abi.MF_TICK if rng.random() < 0.4 else 0      # tick_timeout: make_rpcs/1
         _ = self_
+    if transfers > 0.0:
+        _mix_in_transfers(rng, m, st, n_members, transfers)
     return m
+
+
+def _mix_in_transfers(rng, m, st, n_members, share):
+    for q in range(len(m)):
+        s = int(m["server"][q])
+        row = st[s]
+        awaiting = (int(row["role"]) == abi.ROLE_AWAIT_CONDITION and
+                    int(row["cond_reason"]) == abi.COND_TRANSFER_LEADERSHIP)
+        u = rng.random()
+        if u < share:
+            nxt = ra_log_next_index(row)
+            level = [j for j in range(n_members) if int(row["next_index"][j]) == nxt]
+            choices = [int(row["self"]), abi.NONE, min(n_members, 7)] + level * 3 + list(range(n_members))
+            rec = np.zeros(1, dtype=abi.MSG_DTYPE)
+            rec["server"], rec["kind"], rec["from"] = s, abi.MSG_TRANSFER_LEADERSHIP, int(rng.choice(choices))
+            m[q] = rec[0]
+        elif awaiting and u < share + 0.1:
+            rec = np.zeros(1, dtype=abi.MSG_DTYPE)
+            rec["server"], rec["kind"] = s, abi.MSG_AWAIT_TIMEOUT
+            m[q] = rec[0]
+        elif awaiting and int(m["kind"][q]) == abi.MSG_AER and u < share + 0.6:
+            m["term"][q] = int(row["current_term"]) + int(rng.integers(1, 3))
 
 
 def sort_rpcs(r: np.ndarray) -> np.ndarray:

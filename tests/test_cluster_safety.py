@@ -23,7 +23,7 @@ def run_lossy_then_heal(eng, G, N, seed, lossy_ticks=500, heal_ticks=500, **kw):
     for t in range(heal_ticks):
         sim.step()
         sim.check_safety()
-    sim.p_command = sim.p_query = sim.p_snapshot = 0.0   # let the tail replicate: run until nothing is in flight
+    sim.p_command = sim.p_query = sim.p_snapshot = sim.p_transfer = 0.0   # let the tail replicate: run until nothing is in flight
     calm = 0
     for t in range(3000):
         sim.step()
@@ -126,9 +126,46 @@ def test_closed_loop_clusters_with_wal_outages(oracle_lib, n_members, seed):
         assert sim.stats["transfer_leadership"] == 0     # no peer to hand over to (src/ra_server.erl:661-662)
 
 
+# (few spontaneous election timeouts: a group's election budget, which bounds the runs in its members' run tables, goes
+# to the hand-overs)
+TRANSFER_KW = dict(p_transfer=0.04, max_leaders=12, p_election=0.006)
+
+
+def check_transfers(sim, n_members):
+    """What a run with p_transfer > 0 must have seen (found with the checker alone, before any device took part)."""
+    st = sim.stats
+    if n_members == 1:                                   # nobody to hand over to: already_leader / unknown_member only
+        assert st["transfer_refused"] > 0 and st["transfer_ok"] == 0, st
+        assert sim.transfer_codes == {abi.CALL_ALREADY_LEADER, abi.CALL_UNKNOWN_MEMBER}, sim.transfer_codes
+        return
+    for k in ("transfer_ok", "transfer_refused", "transfer_completed", "transfer_timed_out"):
+        assert st[k] > 0, (k, st)
+    assert abi.CALL_OK in sim.transfer_codes and len(sim.transfer_codes) > 1, sim.transfer_codes
+
+
+@pytest.mark.parametrize("n_members,seed,wal_down", [(3, 51, False), (5, 52, False), (7, 53, False), (1, 54, False),
+                                                     (5, 55, True)])
+def test_closed_loop_clusters_with_leadership_transfers(oracle_lib, n_members, seed, wal_down):
+    """The same, with clients that call {transfer_leadership, Target} on the leader now and then (src/ra.erl:1156-1173,
+    src/ra_server.erl:996-1035): an accepted call parks the leader in await_condition while the target, told to time out
+    at once, runs for the next term; the old leader is released by the new one's first append_entries_rpc or becomes
+    leader again on await_condition_timeout.  Election safety, log matching, state-machine safety and leader
+    completeness after every tick with leaders parked in the transfer condition, convergence at the end.  The last
+    case adds WAL outages: the transfer_leadership hint of a leader's wal_down timeout is then the call itself."""
+    G = 6
+    cpu = oracle_lib.Oracle(G, n_members)
+    cpu.set_state(0, abi.empty_server_states(G, n_members))
+    kw = dict(TRANSFER_KW, p_wal_down=0.01) if wal_down else TRANSFER_KW
+    sim = run_lossy_then_heal(cpu, G, n_members, seed, lossy_ticks=700, heal_ticks=400, **kw)
+    check_converged(sim, G, n_members)
+    check_transfers(sim, n_members)
+    if wal_down:
+        assert sim.stats["transfer_leadership"] > 0, sim.stats
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_members,seed,snapshots", [(3, 11, False), (5, 12, False), (7, 13, False), (5, 14, True),
-                                                      (5, 15, "wal_down")])
+                                                      (5, 15, "wal_down"), (5, 16, "transfers")])
 def test_gpu_gives_identical_decisions_on_closed_loop_streams(oracle_lib, n_members, seed, snapshots):
     """The streams a live cluster produces (elections, repairs after drops, overwrites by new leaders,
     stale rpcs) replayed through the HIP engine: decisions, rpcs and states bit-identical
@@ -142,8 +179,11 @@ def test_gpu_gives_identical_decisions_on_closed_loop_streams(oracle_lib, n_memb
     cpu = oracle_lib.Oracle(G, n_members)
     st0 = abi.empty_server_states(G, n_members)
     cpu.set_state(0, st0)
-    kw = dict(p_snapshot=0.03, max_leaders=11, drop=0.15) if snapshots is True else WAL_DOWN_KW if snapshots else {}
+    kw = dict(p_snapshot=0.03, max_leaders=11, drop=0.15) if snapshots is True else \
+        TRANSFER_KW if snapshots == "transfers" else WAL_DOWN_KW if snapshots else {}
     sim = run_lossy_then_heal(cpu, G, n_members, seed, lossy_ticks=250, heal_ticks=150, **kw)
+    if snapshots == "transfers":
+        check_transfers(sim, n_members)
     ref = oracle_lib.Oracle(G, n_members)
     ref.set_state(0, st0)
     seen = 0

@@ -114,14 +114,16 @@ def test_kernel_code_with_bounded_run_tables(emu_lib, oracle_lib, n_members, see
     assert overflows > 0
 
 
-@pytest.mark.parametrize("n_members,seed,snapshots", [(3, 41, False), (5, 42, True)])
+@pytest.mark.parametrize("n_members,seed,snapshots", [(3, 41, False), (5, 42, True), (5, 44, "transfers")])
 def test_kernel_code_on_closed_loop_cluster_streams(emu_lib, oracle_lib, n_members, seed, snapshots):
-    from test_cluster_safety import run_lossy_then_heal
+    from test_cluster_safety import run_lossy_then_heal, check_transfers, TRANSFER_KW
     G = 8
     st0 = abi.empty_server_states(G, n_members)
     cpu = oracle_lib.Oracle(G, n_members); cpu.set_state(0, st0)
-    kw = dict(p_snapshot=0.03, max_leaders=11, drop=0.15) if snapshots else {}
+    kw = dict(p_snapshot=0.03, max_leaders=11, drop=0.15) if snapshots is True else TRANSFER_KW if snapshots else {}
     sim = run_lossy_then_heal(cpu, G, n_members, seed, lossy_ticks=250, heal_ticks=150, **kw)
+    if snapshots == "transfers":
+        check_transfers(sim, n_members)             # leaders handed over, on the checker, before the kernels replay it
     ref = oracle_lib.Oracle(G, n_members); ref.set_state(0, st0)
     emu = Emu(emu_lib, G, n_members, specialised=True); emu.set_state(0, st0)
     for t, h in enumerate(sim.history):

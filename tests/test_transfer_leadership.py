@@ -7,7 +7,7 @@ handle_await_condition/2 :1916-1959).
 * the boundary: reason 5 round-trips through upload / download and 6 is refused, kind 16 is accepted and 17 refused;
 * the same answer on every path: ticks that mix transfers (and servers awaiting one) into the ordinary random mix
   give byte-identical decisions and state through rgb_submit / rgb_collect, rgb_run_ticks_device with and without
-  kind counts, and a train launch.
+  kind counts, and a train launch -- and those are the decisions and the state of the sequential CPU checker.
 
 Each test runs on the CPU emulation of the HIP sources (emulated_engine) and, under -m gpu, on the MI355X."""
 import json
@@ -245,7 +245,7 @@ def with_transfers(rng, m, st, N):
     return m
 
 
-def check_every_path(engine, G, N, T, seed, on_gpu):
+def check_every_path(engine, oracle_lib, G, N, T, seed, on_gpu):
     from ra_amd import engine as engine_mod
     train_bucket = engine_mod.train_bucket
     rng = np.random.default_rng(seed)
@@ -253,19 +253,35 @@ def check_every_path(engine, G, N, T, seed, on_gpu):
     eng = engine.RaGpuBatch(G, N, max_runs=16, ring_slots=2, ring_capacity=S)
     st0 = mixed_ticks_states(rng, G, N)
     eng.set_state(0, st0)
+    cpu = oracle_lib.Oracle(G, N, max_runs=16)                        # the sequential checker, bounded like the device
+    cpu.set_state(0, st0)
     ticks, want_dec, codes = [], [], set()
     for t in range(T):
         st = eng.get_state()
         m = with_transfers(rng, fuzz.random_msgs(rng, st, N), st, N)
         m = m[np.argsort(train_bucket(m["kind"], m["flags"], m["server"], N), kind="stable")]   # bucket order
         dec, _ = eng.step(m)                                           # rgb_submit / rgb_collect: class kernels
+        do, _ = cpu.step(m)
+        assert dec.tobytes() == do.tobytes(), f"rgb_submit against the checker: tick {t}"
+        assert eng.get_state().tobytes() == cpu.get_state().tobytes(), f"state against the checker: tick {t}"
         ticks.append(m)
         want_dec.append(dec)
         tr = dec[m["kind"] == abi.MSG_TRANSFER_LEADERSHIP]
         assert np.all(tr["flags"] & abi.F_CALL_REPLY | (tr["role"] == abi.ROLE_AWAIT_CONDITION))
         codes |= set(int(c) for c in tr["reply_next_index"][(tr["flags"] & abi.F_CALL_REPLY) != 0])
     st_end = eng.get_state()
+    cpu.close()
     assert codes == set(range(6)), codes                              # every reply of the call came up
+    replay_on_the_device_paths(eng, S, N, st0, ticks, want_dec, st_end, on_gpu)
+    eng.close()
+
+
+def replay_on_the_device_paths(eng, S, N, st0, ticks, want_dec, st_end, on_gpu):
+    """Ticks in bucket order (at most one message per server) from st0 through rgb_run_ticks_device with and without
+    kind counts and through one train launch: the decisions of every tick must be want_dec, the final state st_end."""
+    from ra_amd import engine as engine_mod
+    train_bucket = engine_mod.train_bucket
+    T = len(ticks)
     tb = S * 64
     msgs = Buf(T * tb, on_gpu)
     host = np.zeros(T * tb, dtype=np.uint8)
@@ -304,16 +320,15 @@ def check_every_path(engine, G, N, T, seed, on_gpu):
     assert flags == 0
     compare(dec, "train launch")
     plan.close()
-    eng.close()
 
 
 @pytest.mark.parametrize("G,N,T,seed", [(64, 3, 6, 71), (48, 5, 6, 72), (32, 8, 5, 73)])
-def test_every_path_gives_the_same_answer_on_the_emulated_engine(emulated_engine, G, N, T, seed):
-    check_every_path(emulated_engine, G, N, T, seed, False)
+def test_every_path_gives_the_same_answer_on_the_emulated_engine(emulated_engine, oracle_lib, G, N, T, seed):
+    check_every_path(emulated_engine, oracle_lib, G, N, T, seed, False)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("G,N,T,seed", [(4096, 5, 8, 81), (2048, 3, 8, 82), (1024, 7, 6, 83)])
-def test_every_path_gives_the_same_answer_on_the_gpu(G, N, T, seed):
+def test_every_path_gives_the_same_answer_on_the_gpu(oracle_lib, G, N, T, seed):
     from ra_amd import engine
-    check_every_path(engine, G, N, T, seed, True)
+    check_every_path(engine, oracle_lib, G, N, T, seed, True)

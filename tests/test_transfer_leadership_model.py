@@ -5,8 +5,8 @@ roles' catch-all reply (:1186-1188, 1276-1278, 1655-1657) and the await conditio
 Where the reference re-processes the message in another role ({next_event, Msg}), the engine's one decision is
 checked as two steps: the modelled role change, then the unchanged checker on the intermediate follower state (as
 tests/test_election_model.py does).  request_vote_rpc, pre_vote_rpc, election_timeout and the ra_log events, which
-the reference serves before any predicate (:1918-1931, 1946-1949), are compared with the checker on the same server
-uploaded with COND_MISSING instead (the checker does not know the transfer condition)."""
+the reference serves before any predicate (:1918-1931, 1946-1949), are compared with the checker twice: on the same
+server awaiting COND_MISSING instead (the clauses do not look at the condition), and on the server as it is."""
 import numpy as np
 import pytest
 
@@ -220,6 +220,16 @@ def check_condition(eng, oracle_lib, n, seed):
             d2 = d2.copy(); d2["server"] = sv
             assert got.tobytes() == row1.tobytes(), tag
             assert d2[0].tobytes() == d.tobytes(), (tag, d2[0], d)
+            # and the checker holding the server as it is, in the transfer condition
+            grp, i = one_group(before, sv, n, row0)
+            two = oracle_lib.Oracle(1, n)
+            two.set_state(0, grp)
+            d3, _ = two.step(np.array([m2], dtype=abi.MSG_DTYPE))
+            got = two.get_state()[i]
+            two.close()
+            d3 = d3.copy(); d3["server"] = sv
+            assert got.tobytes() == row1.tobytes(), tag
+            assert d3[0].tobytes() == d.tobytes(), (tag, d3[0], d)
             seen["served_first"] += 1
         elif k == abi.MSG_AWAIT_TIMEOUT:                              # :1932-1945 with the timeout map of :1027-1028
             want = row0.copy()
