@@ -20,7 +20,21 @@
 #define UNDEF 0xFFFFFFFFFFFFFFFFull
 #define SLOT_NONE4 0xFu
 
-/* Profiling knobs exist only in the -DRGB_PROFILE build (libra_gpu_batch_prof.so, used by tools/): the
+/* Build-time switches (-D) of this file -- every one there is; the product is built with none of them:
+ *   RGB_HOST_EMULATION            the same sources compiled for the CPU (tests/native/)
+ *   RGB_PROFILE                   the profiling knobs below (libra_gpu_batch_prof.so)
+ *   RGB_X_ONLY_N=n                instantiate the kernels for groups of n members only (tools/, resource gates)
+ *   RGB_X_MARK                    comment markers around every class path in the assembly (tools/class_isa.py)
+ *   RGB_X_DECLINE_HIST            why lanes declined their fast path, counted into dbg_buf (tools/decline_hist.py)
+ *   RGB_X_TRAIN_TIMELINE          per-wavefront wall-clock stamps of a train launch (tools/train_timeline.py)
+ *   RGB_TICK_BLOCK                threads per block of the tick kernels (64: one wavefront)
+ *   RGB_MIN_WAVES(N), RGB_CLASS_MIN_WAVES(N), RGB_TRAIN_MIN_WAVES(N), RGB_TRAIN_PERSIST_MIN_WAVES(N)
+ *                                 wavefronts per SIMD the register allocator leaves room for, per kernel family
+ *   RGB_TRAIN_SPIN_LIMIT          polls before a train wavefront gives up on a dependency
+ *   RGB_TRAIN_SLEEP               s_sleep argument between two polls
+ * The switches earlier rounds timed alternatives with are gone: profiles/EXPERIMENTS.md, "Retired switches".
+ *
+ * Profiling knobs exist only in the -DRGB_PROFILE build (libra_gpu_batch_prof.so, used by tools/): the
  * product library has no run-time switch that changes what a tick computes.
  *   1 = no state write-back, 2 = no decision store, 8 = no hot-line load (zero state),
  *   16 = per-wave timestamps into dbg_buf, 32 = run-table probes answer from the last run (no dependent
@@ -48,44 +62,24 @@ namespace {
  * when the peers row is one 128-byte line (3..5 members): their wavefronts fetch the peers rows WITH the hot rows --
  * one round trip, 8 lanes per line, into the LDS half the other 32 hot rows would have used -- instead of a second,
  * per-lane round trip once the clause code starts. */
-#ifndef RGB_X_LEAD32
-#define RGB_X_LEAD32 1
-#endif
 __host__ __device__ constexpr bool rgb_lead_class(int c) { return c == 1 || c == 3 || c == 4; }
+__host__ __device__ __forceinline__ constexpr u32 rgb_class_slice(int c, unsigned n_members) {
+  return (rgb_lead_class(c) && ((3u * n_members + 7u) & ~7u) == 16u) ? 32u : (u32)RGB_TICK_BLOCK;
+}
 /* classes whose kinds only use the first 32 bytes of their message records (include/ra_gpu_batch.h, "Field use by
  * kind": term, a, b at most; the two-range form of a written event re-reads its record): written, pipeline_rpcs,
  * request_vote, vote_result, await_timeout, snapshot_written, heartbeat_rpc, heartbeat_reply, consistent_query.
  * Their wavefronts request half of every record -- a third of a tick's messages, and a tick's time follows its bytes */
-#ifndef RGB_X_HINT
-#define RGB_X_HINT 1        /* the generator's steady-state bucketing hint (rgb_bucket_hinted); 0: A/B timing only */
-#endif
-#ifndef RGB_X_HALFMSG
-#define RGB_X_HALFMSG 1
-#endif
 __host__ __device__ constexpr bool rgb_half_msg_class(int c) {
-  return RGB_X_HALFMSG && (c == 2 || c == 4 || c == 5 || c == 6 || c == 7 || c == 11 || c == 12 || c == 13 || c == 14);
-}
-__host__ __device__ __forceinline__ constexpr u32 rgb_class_slice(int c, unsigned n_members) {
-  return (RGB_X_LEAD32 && rgb_lead_class(c) && ((3u * n_members + 7u) & ~7u) == 16u) ? 32u : (u32)RGB_TICK_BLOCK;
+  return c == 2 || c == 4 || c == 5 || c == 6 || c == 7 || c == 11 || c == 12 || c == 13 || c == 14;
 }
 /* TRAIN launches: the leader-side classes of groups of six to eight members (peers rows of 192 bytes) take 32 messages
  * too -- their wavefronts fetch the 32 peers rows cooperatively into LDS (12 lanes per row, 256 bytes of LDS each)
  * beside the 32 hot rows and the first line of the 32 run tables (16 KiB, what these kernels allocate anyway), where
  * every lane used to read its row from memory with eleven 16-byte loads of its own (round 5; BASELINE configs[4]) */
-#ifndef RGB_X_NORPC
-#define RGB_X_NORPC 0             /* 1: PROBE (breaks the output) -- no rpc record is stored: what the records' stores cost a tick */
-#endif
-#ifndef RGB_X_LEAD32_WIDE
-#define RGB_X_LEAD32_WIDE 1
-#endif
-#ifndef RGB_TRAIN_RUNS_LDS
-#define RGB_TRAIN_RUNS_LDS 1      /* the first line of a train wavefront's run tables comes into LDS with its rows */
-#endif
 __host__ __device__ __forceinline__ constexpr bool rgb_wide_peers(unsigned n_members) { return ((3u * n_members + 7u) & ~7u) == 24u; }
 __host__ __device__ __forceinline__ constexpr u32 rgb_train_class_slice(int c, unsigned n_members) {
-  /* (16 KiB of LDS per wavefront: the kernels built without the run-table line allocate less) */
-  return (RGB_X_LEAD32 && RGB_X_LEAD32_WIDE && RGB_TRAIN_RUNS_LDS && rgb_lead_class(c) && rgb_wide_peers(n_members)) ? 32u
-                                                                                                                  : rgb_class_slice(c, n_members);
+  return (rgb_lead_class(c) && rgb_wide_peers(n_members)) ? 32u : rgb_class_slice(c, n_members);
 }
 
 
@@ -106,14 +100,11 @@ __device__ __forceinline__ void store16_nt(void *p, ulonglong2 v) {
 /* One 56-byte rgb_rpc record (seven words, 8-byte aligned: records are 56 bytes apart) as three 16-byte stores and one
  * of 8 -- gfx950 takes a 16-byte store at any dword alignment -- instead of seven 8-byte stores (round 6: the records'
  * stores, 28 instructions per pipelining lane on the longest-lived wavefronts of a tick, cost 6-7 % of it by the
- * no-store probe; RGB_X_RPC_ST8 = 1 is the old form for A/B timing) */
-#ifndef RGB_X_RPC_ST8
-#define RGB_X_RPC_ST8 0
-#endif
+ * no-store probe) */
 typedef unsigned long long rgb_u64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
 __device__ __forceinline__ void store_rpc(rgb_rpc *slot, u64 w0, u64 w1, u64 w2, u64 w3, u64 w4, u64 w5, u64 w6) {
   u64 *o = reinterpret_cast<u64 *>(slot);
-#if RGB_X_RPC_ST8 || defined(RGB_HOST_EMULATION)
+#ifdef RGB_HOST_EMULATION
   ST8(o + 0, w0); ST8(o + 1, w1); ST8(o + 2, w2); ST8(o + 3, w3); ST8(o + 4, w4); ST8(o + 5, w5); ST8(o + 6, w6);
 #else
   rgb_u64x2_a8 a, b, c;
@@ -128,15 +119,12 @@ __device__ __forceinline__ void store_rpc(rgb_rpc *slot, u64 w0, u64 w1, u64 w2,
  * -- inside the clause code of the longest-lived wavefronts of a tick ({commands}: four records per lane) -- they stand
  * in front of the wavefront's publish twice: their issue, and their acknowledgements in the wait before it.  A train
  * wavefront keeps what it cannot recompute (32 bytes per record) in LDS and stores the records BEHIND its publish, like
- * its decisions.  Same records, same slots.  RGB_X_RPC_DEFER = 0: the direct form, A/B timing */
-#ifndef RGB_X_RPC_DEFER
-#define RGB_X_RPC_DEFER 1
-#endif
+ * its decisions.  Same records, same slots. */
 template <class Lane>
 __device__ __forceinline__ void emit_rpc(Lane &L, rgb_rpc *rpcs, u32 slot_base, unsigned ord, u32 msg_index, u64 w1,
                                          u64 rp_idx, u64 rp_term, u64 new_ni) {
-  if (rpcs == nullptr || RGB_X_NORPC) return;
-  if (RGB_X_RPC_DEFER && L.rpc_stash != nullptr && ord < 4u) {
+  if (rpcs == nullptr) return;
+  if (L.rpc_stash != nullptr && ord < 4u) {
     L.rpc_stash[2u * ord] = make_ulonglong2(w1, rp_idx);
     L.rpc_stash[2u * ord + 1u] = make_ulonglong2(rp_term, new_ni);
     return;
@@ -393,9 +381,6 @@ __device__ __forceinline__ bool range_nonempty(const Lane &L) { return L.first <
  * run, on the critical path of the wavefront's life.  The table is read-only for these kinds (a leader never truncates
  * its own log; a pushed run stays in registers until the commit). */
 #define RGB_RUNS_LDS 8
-#ifndef RGB_TRAIN_RUNS_LDS     /* (default set in front of rgb_train_class_slice) */
-#define RGB_TRAIN_RUNS_LDS 1
-#endif
 /* (start, term) of in-memory run k */
 template <class Lane>
 __device__ __forceinline__ ulonglong2 run_pair(const Lane &L, int k) {
@@ -2023,11 +2008,7 @@ __device__ __forceinline__ void make_decision(Dec &d, u32 server, unsigned role,
 /* The compact form of a decision (include/ra_gpu_batch.h, "Compact decisions"): applied where a decision is staged for
  * its store, whatever path computed it; returns whether the record became 32 bytes.  Three shapes, each tested value
  * by value -- what does not fit stays a full record. */
-#ifndef RGB_X_COMPACT
-#define RGB_X_COMPACT 1
-#endif
 __device__ __forceinline__ bool compact_decision(Dec &d) {
-  if (!RGB_X_COMPACT) return false;
   const u32 flags = (u32)d.w[1];
   const unsigned kind = (unsigned)(d.w[0] >> 56);
   if ((d.w[1] >> 32) != 0ull || (flags & RGB_F_COMPACT)) return false;             /* invariant / masks in use */
@@ -2132,23 +2113,12 @@ __device__ __forceinline__ void process_message(const rgb_dev &dev, const ulongl
   L.peers_lds = prepeers; L.peers_swz = swz; L.pdirty = 0;
   L.runs_lds = preruns;
   /* PL: the class kernel fetched this leader-side message's peers row into LDS with the hot row (128-byte rows:
-   * 3..5 members): the clause code reads and writes it there, no register copy */
-#ifndef RGB_X_COMMIT_WAIT
-#define RGB_X_COMMIT_WAIT 1
-#endif
-#ifndef RGB_X_PL
-#define RGB_X_PL 0     /* measured 1 % slower than the register arrays on the aged stream (23.6 vs 23.4 us), although it
-                          removes every spill of the leader-side classes: kept as an option */
-#endif
-#ifndef RGB_X_PL_TICK
-#define RGB_X_PL_TICK 1   /* the per-tick class kernel (4 wavefronts per SIMD, 128 registers): the peers row stays in LDS and
-                             the commit re-reads the hot row from LDS (RGB_X_REREAD_TICK) -- no spills, where the register
-                             arrays spilled 34 VGPRs (40 bytes of scratch per lane) */
-#endif
-#ifndef RGB_X_REREAD_TICK
-#define RGB_X_REREAD_TICK 1
-#endif
-  constexpr bool PL = (TR ? RGB_X_PL : RGB_X_PL_TICK) && PRE && rgb_class_slice(1, (unsigned)N) == 32u &&
+   * 3..5 members): the clause code reads and writes it there, no register copy.
+   * Only the per-tick class kernel (4 wavefronts per SIMD, 128 registers): there the peers row stays in LDS and the
+   * commit re-reads the hot row from LDS -- no spills, where the register arrays spilled 34 VGPRs (40 bytes of scratch
+   * per lane).  Not the train: it measured 1 % slower than the register arrays on the aged stream (23.6 vs 23.4 us),
+   * although it removes every spill of the leader-side classes */
+  constexpr bool PL = !TR && PRE && rgb_class_slice(1, (unsigned)N) == 32u &&
                       (KIND == RGB_MSG_AER_REPLY || KIND == RGB_MSG_APPEND || KIND == RGB_MSG_PIPELINE_RPCS);
   if (!PL && (L.kind == RGB_MSG_AER_REPLY || L.kind == RGB_MSG_APPEND || L.kind == RGB_MSG_PIPELINE_RPCS ||
               L.kind == RGB_MSG_TRANSFER_LEADERSHIP) &&
@@ -2230,7 +2200,7 @@ __device__ __forceinline__ void process_message(const rgb_dev &dev, const ulongl
   }
 
   /* ---- commit: run table ---- */
-#if RGB_X_COMMIT_WAIT && !defined(RGB_HOST_EMULATION)
+#ifndef RGB_HOST_EMULATION
   /* every load of the clause code has been consumed by now (the new state depends on them); saying so keeps the
    * compiler from putting a vmcnt(0) -- which on gfx950 also waits for the STORES below to be acknowledged -- in
    * front of the first use of the decision words after the function returns */
@@ -2323,10 +2293,7 @@ __device__ __forceinline__ void process_message(const rgb_dev &dev, const ulongl
   ulonglong2 *ho = reinterpret_cast<ulonglong2 *>(hot);
   if (!RGB_KNOB(dev, 1u)) {
   if (L.n_runs < 2) { L.prs = 0; L.prt = 0; }         /* canonical: no run n-2 */
-#ifndef RGB_X_REREAD
-#define RGB_X_REREAD 0
-#endif
-  if ((TR ? RGB_X_REREAD : RGB_X_REREAD_TICK) && PRE) {
+  if (!TR && PRE) {
     /* what the row held: re-read from the LDS row (still intact) instead of kept in sixteen registers across the
      * clause code */
 #pragma unroll
@@ -2409,9 +2376,6 @@ __device__ __forceinline__ bool fuse_wanted(const rgb_dev &dev, const Dec &d) {
  * hold they produce the decision and the state changes process_message<N, KIND> would have produced, bit for bit
  * (the parity tests run every stream through both); when any fails they touch nothing and return false.
  * Row pieces are read from the lane's LDS row (piece p at pre[p ^ swz]). */
-#ifndef RGB_X_FAST
-#define RGB_X_FAST 1
-#endif
 /* -DRGB_X_DECLINE_HIST (tools/decline_hist.py): why a lane declined its fast path, counted per class and reason in
  * dev.dbg_buf (word 0 of every class = lanes that took the fast path) */
 #if defined(RGB_X_DECLINE_HIST) && !defined(RGB_HOST_EMULATION)
@@ -2428,20 +2392,16 @@ __device__ __forceinline__ bool fuse_wanted(const rgb_dev &dev, const Dec &d) {
  * only record what they want stored and the wavefront stores it in PAIRS of lanes: in each of two instructions lanes
  * 2k and 2k+1 write the two pieces of ONE server -- 32 contiguous bytes, one request -- so an instruction touches 32
  * lines.  (lanes that took no fast path record nothing) */
-#ifndef RGB_X_PAIR_STORE
-#define RGB_X_PAIR_STORE 1
-#endif
 struct PairSt {
   ulonglong2 *p;          /* the first piece of the unit */
   ulonglong2 a, b;
   unsigned m;             /* bit 0: store a at p, bit 1: store b at p + 1 */
 };
 __device__ __forceinline__ void pair_record(PairSt *ps, ulonglong2 *p, bool sa, const ulonglong2 a, bool sb, const ulonglong2 b) {
-  if (RGB_X_PAIR_STORE && ps != nullptr) {
+  /* (both callers pass their wavefront's record: the test folds away once this is inlined, and is kept because
+   * without it the compiler allocates the slice kernels' registers differently) */
+  if (ps != nullptr) {
     ps->p = p; ps->a = a; ps->b = b; ps->m = (sa ? 1u : 0u) | (sb ? 2u : 0u);
-  } else {
-    if (sa) ST16(p, a);
-    if (sb) ST16(p + 1, b);
   }
 }
 __device__ __forceinline__ u64 shfl64(u64 v, int src) {
@@ -2468,7 +2428,7 @@ __device__ __forceinline__ void pair_store(const PairSt &st, u32 lane) {
  * src/ra_log.erl:547-599; evaluate_commit_index_follower/2 :2246-2280) */
 __device__ __forceinline__ bool fast_aer(const rgb_dev &dev, const ulonglong2 m0, const ulonglong2 m1, const ulonglong2 m2,
                                          const ulonglong2 m3, const ulonglong2 *pre, unsigned swz, Dec &out,
-                                         PairSt *pst = nullptr) {
+                                         PairSt *pst) {
   const u32 server = (u32)(m0.x & 0xFFFFFFFFull);
   const unsigned wire_kind = (unsigned)((m0.x >> 32) & 0xFF), from = (unsigned)((m0.x >> 40) & 0xFF);
   const unsigned mflags = (unsigned)((m0.x >> 48) & 0xFF), gap = (unsigned)((m0.x >> 56) & 0xFF);
@@ -2522,7 +2482,7 @@ __device__ __forceinline__ bool fast_aer(const rgb_dev &dev, const ulonglong2 m0
  * last_written moves to To, the reply goes to the known leader (src/ra_server.erl:1457-1474; ra_log:handle_event
  * src/ra_log.erl:897-920) */
 __device__ __forceinline__ bool fast_written(const rgb_dev &dev, const ulonglong2 m0, const ulonglong2 m1,
-                                             const ulonglong2 *pre, unsigned swz, Dec &out, PairSt *pst = nullptr) {
+                                             const ulonglong2 *pre, unsigned swz, Dec &out, PairSt *pst) {
   const u32 server = (u32)(m0.x & 0xFFFFFFFFull);
   const unsigned wire_kind = (unsigned)((m0.x >> 32) & 0xFF), mflags = (unsigned)((m0.x >> 48) & 0xFF);
   if (wire_kind != RGB_MSG_WRITTEN || server >= dev.n_servers || mflags != 0) FP_DECLINE(2, 1);
@@ -2818,11 +2778,12 @@ __device__ __forceinline__ u32 rgb_xcc_id() {
 #define RGB_TRAIN_SPIN_LIMIT 20000u    /* x ~4 us per try once backed off: ~80 ms */
 #endif
 #endif
-
-#ifndef RGB_X_TICKET_AT
-#define RGB_X_TICKET_AT 0   /* where a persistent wavefront requests its next row: 0 behind its publish, 1 in front of its
-                               clause code (the rows have arrived), 2 at the start of its slice */
+#ifndef RGB_TRAIN_SLEEP
+#define RGB_TRAIN_SLEEP 4   /* x 64 clocks: ~0.1 us between polls.  The closed loop does not care (2..32 within noise, rounds 3
+                               and 6); the chain-bound literal config 3, whose wavefronts all wait, runs 3 % faster with 4 than
+                               with 8 or 16 (7.10-7.17 against 7.35-7.47 us per tick, same box, round 6) */
 #endif
+
 /* Persistent train launches: a wavefront takes the next row of its shard from the shard's ticket counter: one
  * returning atomic by lane 0.  rgb_take_ticket only ISSUES it (the raw value is valid in lane 0); rgb_ticket_value
  * brings it to the whole wavefront where it is consumed, so the atomic's round trip overlaps whatever is issued in
@@ -2833,11 +2794,7 @@ __device__ __forceinline__ u32 rgb_take_ticket(u32 *ctr, const u32 *err) {
   if (threadIdx.x == 0) v = atomicAdd(ctr, 1u);
   if (threadIdx.x == 1) v = *err;
 #else
-#ifdef RGB_X_TICKET_WG   /* EXPERIMENT: no sc1 on the atomic (all users of a counter share one XCD's L2) */
-  if (threadIdx.x == 0) v = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
   if (threadIdx.x == 0) v = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
   /* lane 1 of the same register: the launch's error word (a failed launch drains instead of computing on) */
   if (threadIdx.x == 1) v = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
@@ -2893,7 +2850,7 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
    * peers rows come into LDS cooperatively (rgb_train_class_slice) */
   constexpr bool PEERS_WIDE = TR && rgb_train_class_slice(1, (unsigned)N) == 32u && !PEERS_LDS;
   /* a table row of max_runs >= 8 runs holds the whole 128-byte line that is fetched (wave-uniform) */
-  const bool RUNS_LDS = TR && RGB_TRAIN_RUNS_LDS && (PEERS_LDS || PEERS_WIDE) && dev.max_runs >= (u32)RGB_RUNS_LDS;
+  const bool RUNS_LDS = TR && (PEERS_LDS || PEERS_WIDE) && dev.max_runs >= (u32)RGB_RUNS_LDS;
   /* groups of six and more members (no peers rows in LDS: the area is free): an append_entries_rpc wavefront whose
    * messages point below the current term's entries (prev_log_term != term in any lane: log-matching repair, the
    * configs[4] workload) will walk its servers' run tables -- their first line comes with the hot rows (decided
@@ -2909,7 +2866,6 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
 #define RGB_TT(k) do { } while (0)
 #endif
   RGB_TT(0);
-  if (TR && RGB_X_TICKET_AT == 2 && ticket_ctr != nullptr) *next_ticket = rgb_take_ticket(ticket_ctr, ctl);
   const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(msgs + base);
   /* a train's stamp byte travels with the record copies: requested here, it arrives under their round trip (behind
    * the records' barrier it was a second memory round trip in front of the first poll) */
@@ -2948,7 +2904,7 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
     if (cls == 2 && active && (((m0.x >> 48) & 0xFFull) & RGB_MF_SEQ2)) m3 = ld16<true>(src + lane * 4u + 3u);
   }
   RGB_TT(1);
-  if (TR && RGB_TRAIN_RUNS_LDS && !PEERS_LDS && cls == 0 && dev.max_runs >= (u32)RGB_RUNS_LDS)
+  if (TR && !PEERS_LDS && cls == 0 && dev.max_runs >= (u32)RGB_RUNS_LDS)
     AER_RUNS = __ballot(active && m1.y != m0.y) != 0ull;
   const u32 sv = (u32)(m0.x & 0xFFFFFFFFull);
   /* the message addresses a server (a NOP or an out-of-range id touches no state and has no stamp) */
@@ -2967,32 +2923,16 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
     need = has_srv ? need_raw : 0u;
     unsigned spins = 0;
     bool late = has_srv;
-#ifdef RGB_X_TRAIN_NODEPS
-    /* EXPERIMENT builds (never in the product; break parity; bench.py --snapshot-kernel: the rows of an in-launch
-     * snapshot wait for exact bytes): 1 = no poll at all -- the tick without the dependency waits AND without the
-     * poll's round trip (what a sequence tag inside the row could give at best); 2 = one poll whose answer is
-     * ignored -- without the waits only.  Round 5, same box: 17.46 us per tick, 16.72 with 2, 16.36 with 1 */
-    if (RGB_X_TRAIN_NODEPS == 1 || RGB_X_TRAIN_NODEPS == 3) late = false;
-#endif
     for (;;) {
       /* only the lanes that are still waiting poll again; a wavefront that has to wait backs off (thousands of
        * waiting wavefronts polling flat out starve the ones they wait for of L2 bandwidth) */
       if (late) {
 #ifdef RGB_HOST_EMULATION
         const unsigned cur = *seqp;
-#elif defined(RGB_X_POLL32)
-        /* EXPERIMENT (round 5, neutral: 15.95 / 16.13 against 15.94 / 16.02 us per tick): the poll as a load of the byte's
-         * DWORD (neighbouring lanes' bytes share dwords and lines) */
-        const uintptr_t pa = reinterpret_cast<uintptr_t>(seqp);
-        const unsigned cur = (__hip_atomic_load(reinterpret_cast<const u32 *>(pa & ~(uintptr_t)3), __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT) >> (8u * (unsigned)(pa & 3u))) & 0xFFu;
 #else
         const unsigned cur = __hip_atomic_load(seqp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
         late = cur != need;
-#ifdef RGB_X_TRAIN_NODEPS
-        if (RGB_X_TRAIN_NODEPS == 2) late = false;
-#endif
       }
       if (__ballot(late) == 0ull) break;
       spins += 1;
@@ -3002,12 +2942,6 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
       bool give_up = spins > RGB_TRAIN_SPIN_LIMIT;
 #ifndef RGB_HOST_EMULATION
       if ((spins & 15u) == 0u && __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) give_up = true;
-#ifndef RGB_TRAIN_SLEEP
-#define RGB_TRAIN_SLEEP 4                                 /* x 64 clocks: ~0.1 us between polls.  The closed loop does not care
-                                                             (2..32 within noise, rounds 3 and 6); the chain-bound literal config 3,
-                                                             whose wavefronts all wait, runs 3 % faster with 4 than with 8 or 16
-                                                             (7.10-7.17 against 7.35-7.47 us per tick, same box, round 6) */
-#endif
       __builtin_amdgcn_s_sleep(RGB_TRAIN_SLEEP);
       if (spins > 64u) __builtin_amdgcn_s_sleep(127);     /* a long wait (> ~15 us) is not the steady state: back off */
 #endif
@@ -3103,7 +3037,6 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
   }
   lds_barrier();
   RGB_TT(3);
-  if (TR && RGB_X_TICKET_AT == 1 && ticket_ctr != nullptr) *next_ticket = rgb_take_ticket(ticket_ctr, ctl);
   const ulonglong2 *hrow = io + lane * 8;
   const unsigned hswz = (lane >> 1) & 7u;
   const ulonglong2 *prow = (PEERS_LDS && lead_cls) ? io + 4 * RGB_TICK_BLOCK + lane * 8
@@ -3123,12 +3056,11 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
    * row -- read into registers before anything is parked -- and store them behind the publish; a fifth and sixth
    * record (groups of six and more members) are stored where they are made.  What a record takes from the server, its
    * current term, is read HERE (a leader that emits records does not change its term in the same message) */
-  const bool STASH = TR && RGB_X_RPC_DEFER && (PEERS_LDS || PEERS_WIDE) && lead_cls && rpcs != nullptr;
+  const bool STASH = TR && (PEERS_LDS || PEERS_WIDE) && lead_cls && rpcs != nullptr;
   ulonglong2 *stash = STASH ? io + lane * 8 : nullptr;
   u64 ct0 = 0;
   if (STASH) ct0 = hrow[HOT_P_TERM ^ hswz].x;
   bool done = false;
-#if RGB_X_FAST
   /* the steady-state outcome of the three bulk kinds first; whoever is left takes the general clause code below */
   PairSt pst;
   pst.p = nullptr; pst.a = pst.b = make_ulonglong2(0, 0); pst.m = 0;
@@ -3137,8 +3069,7 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
     else if (cls == 1) done = fast_aer_reply<N, TR, (PEERS_LDS || PEERS_WIDE)>(dev, m0, m1, hrow, hswz, d, prow, rrow);
     else if (cls == 2) done = fast_written(dev, m0, m1, hrow, hswz, d, &pst);
   }
-  if (RGB_X_PAIR_STORE && (cls == 0 || cls == 2)) pair_store(pst, lane);       /* (wave-uniform) */
-#endif
+  if (cls == 0 || cls == 2) pair_store(pst, lane);       /* (wave-uniform) */
 #if defined(RGB_PROFILE) && !defined(RGB_HOST_EMULATION)
   u64 tf = 0; unsigned n_fast = 0;
   if (!TR && RGB_KNOB(dev, 16u)) { tf = wall_clock64(); n_fast = (unsigned)__popcll(__ballot(done)); }   /* fast paths done */
@@ -3188,7 +3119,7 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
   if (TR) {
     /* 4. publish: every state store of this wavefront has been acknowledged by the L2 (inline assembly: the
      * compiler's wait-count pass must not drop or move it), then the advanced sequence byte of every server */
-#if !defined(RGB_HOST_EMULATION) && !defined(RGB_X_TRAIN_NOWAIT)
+#ifndef RGB_HOST_EMULATION
     /* the BUILTIN, like glds_wait(): behind an inline-assembly wait the compiler's wait-count pass no longer knows
      * that the LDS-DMA copies have landed and puts a vmcnt(0) -- i.e. a wait for the previous store's acknowledgement
      * -- in front of every later LDS access: the four decision stores then leave one round trip apart (1.5 us of a
@@ -3196,26 +3127,12 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
     __builtin_amdgcn_s_waitcnt(0x0F70);
     asm volatile("" ::: "memory");
 #endif
-#if defined(RGB_X_TRAIN_NODEPS) && RGB_X_TRAIN_NODEPS == 3
-    /* EXPERIMENT (with NODEPS = 1's missing poll): no sequence-byte store either -- what all of the byte traffic costs */
-    if (RGB_X_TRAIN_NODEPS == 1)
-#endif
-#if defined(RGB_X_XOR_PUBLISH) && !defined(RGB_HOST_EMULATION)
-    /* EXPERIMENT: the byte advanced by a fire-and-forget atomic XOR on its dword (old value = need, known) instead of a
-     * one-byte store */
-    if (has_srv && seqp != nullptr) {
-      const uintptr_t a = reinterpret_cast<uintptr_t>(seqp);
-      (void)__hip_atomic_fetch_xor(reinterpret_cast<u32 *>(a & ~(uintptr_t)3), ((need ^ (need + 1u)) & 0xFFu) << (8u * (unsigned)(a & 3u)),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#else
     if (has_srv && seqp != nullptr) *seqp = (unsigned char)(need + 1u);
-#endif
     /* persistent train: the wavefront's NEXT row is requested now -- behind the publish (the atomic's return must not
      * sit in front of the sequence bytes) and under the decision stores; rgb_train_kernel consumes it at the top of
      * its loop.  Not earlier: a ticket held while this slice runs would start its row a whole wavefront life late,
      * and the rows that depend on it one tick later would find it uncommitted */
-    if (RGB_X_TICKET_AT == 0 && ticket_ctr != nullptr) *next_ticket = rgb_take_ticket(ticket_ctr, ctl);
+    if (ticket_ctr != nullptr) *next_ticket = rgb_take_ticket(ticket_ctr, ctl);
     /* dealt trains: this block's rotation mark, fire and forget (no value comes back, nothing waits for it; behind
      * the publish, so the sequence bytes do not wait for its acknowledgement either) */
     if (place_word != nullptr && lane == 0) {
@@ -3253,22 +3170,15 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
   }
   lds_barrier();
   if (!TR && RGB_KNOB(dev, 2u)) return true;
-#ifdef RGB_X_TRAIN_NODEC      /* EXPERIMENT (breaks the output): no decision stores -- what the decision stream costs a tick */
-  if (TR) return true;
-#endif
   ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(dec + base);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const u32 piece = k * RGB_TICK_BLOCK + lane;
     const u32 j = piece >> 2, part = piece & 3u;
     /* decisions are never re-read on the device: non-temporal (measured -5 % per tick) */
-#ifdef RGB_X_HALFDEC      /* EXPERIMENT (breaks the output): 32-byte decisions -- what would compact records be worth? */
-    if (j < cnt && part < 2u) store16_nt((void *)(dst + piece), io[j * RGB_IO_SLOT + part]);
-#else
     /* the upper half of a compact record is not written */
     if (j < cnt && (part < 2u || !((cmask >> j) & 1ull)))
       store16_nt((void *)(dst + piece), io[j * RGB_IO_SLOT + part]);
-#endif
   }
 #if defined(RGB_X_TRAIN_TIMELINE) && !defined(RGB_HOST_EMULATION)
   if (TR && dev.dbg_buf != nullptr && lane == 0 && blockIdx.x < (1u << 20)) {
@@ -3368,11 +3278,7 @@ __global__ __launch_bounds__(RGB_TICK_BLOCK, RGB_CLASS_MIN_WAVES(N)) void rgb_ti
  * resident wavefronts / wavefront life, and the spills' scratch round trips sit on the clause code's dependency chain
  * -- 4 x 128 measured 24-25 us per tick, 3 x 168 19-20 */
 #ifndef RGB_TRAIN_MIN_WAVES
-#ifdef RGB_X_TRAIN_WAVES            /* (a plain number on the command line: tools/build_variants.sh) */
-#define RGB_TRAIN_MIN_WAVES(N) RGB_X_TRAIN_WAVES
-#else
 #define RGB_TRAIN_MIN_WAVES(N) 3
-#endif
 #endif
 /* the PERSISTENT form of groups of eight members: 167 registers + 2 spilled (12 bytes of scratch) at three wavefronts per
  * SIMD; its 16 KiB of LDS per wavefront admit ten per compute unit anyway, so it is compiled for two per SIMD (eight per
@@ -3417,7 +3323,7 @@ __device__ __forceinline__ bool rgb_train_snap_slice(const rgb_dev &dev, u32 x, 
   const u32 sbase = live ? rgb_seq_index(g * (u32)N, (unsigned)N, dev.seq_stride) : 0u;   /* the members' bytes follow */
   unsigned need[N];
 #pragma unroll
-  for (int m = 0; m < N; ++m) need[m] = live ? (unsigned)stamps[sbase + m * RGB_SEQ_SPREAD] : 0u;
+  for (int m = 0; m < N; ++m) need[m] = live ? (unsigned)stamps[sbase + m] : 0u;
   unsigned spins = 0;
   bool late = live;
   for (;;) {
@@ -3426,9 +3332,9 @@ __device__ __forceinline__ bool rgb_train_snap_slice(const rgb_dev &dev, u32 x, 
 #pragma unroll
       for (int m = 0; m < N; ++m) {
 #ifdef RGB_HOST_EMULATION
-        const unsigned cur = dev.seq[sbase + m * RGB_SEQ_SPREAD];
+        const unsigned cur = dev.seq[sbase + m];
 #else
-        const unsigned cur = __hip_atomic_load(dev.seq + sbase + m * RGB_SEQ_SPREAD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned cur = __hip_atomic_load(dev.seq + sbase + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
         ok = ok && cur == need[m];
       }
@@ -3475,7 +3381,7 @@ __device__ __forceinline__ bool rgb_train_snap_slice(const rgb_dev &dev, u32 x, 
 #endif
   if (live) {
 #pragma unroll
-    for (int m = 0; m < N; ++m) dev.seq[sbase + m * RGB_SEQ_SPREAD] = (unsigned char)(need[m] + 1u);
+    for (int m = 0; m < N; ++m) dev.seq[sbase + m] = (unsigned char)(need[m] + 1u);
   }
   return true;
 }
@@ -3495,8 +3401,7 @@ __device__ __forceinline__ bool rgb_train_snap_slice(const rgb_dev &dev, u32 x, 
 #define RGB_TRAIN_CTL_MARK 320u
 template <int N>
 __global__ __launch_bounds__(RGB_TICK_BLOCK, RGB_TRAIN_MIN_WAVES(N)) void rgb_train_dealt_kernel(rgb_train_args args) {
-  __shared__ ulonglong2 io[!RGB_TRAIN_RUNS_LDS ? RGB_TICK_BLOCK * RGB_HOT_SLOT
-                           : rgb_class_slice(1, (unsigned)N) == 32u ? 12 * RGB_TICK_BLOCK : 16 * RGB_TICK_BLOCK];
+  __shared__ ulonglong2 io[rgb_class_slice(1, (unsigned)N) == 32u ? 12 * RGB_TICK_BLOCK : 16 * RGB_TICK_BLOCK];
   const u32 x = blockIdx.x & (RGB_TRAIN_SHARDS - 1u), k = blockIdx.x / RGB_TRAIN_SHARDS;
   const u32 rpt = args.rpt, n_ticks = args.n_ticks;
   const u32 t = k / rpt, row = k - t * rpt;
@@ -3554,8 +3459,7 @@ template <int N>
 __global__ __launch_bounds__(RGB_TICK_BLOCK, RGB_TRAIN_PERSIST_MIN_WAVES(N)) void rgb_train_kernel(rgb_train_args args) {
   /* records, then hot rows; a leader-side slice: 32 hot rows | 32 peers rows | the first line of 32 run tables
    * (12 KiB: twelve wavefronts per CU -- three per SIMD, what the registers allow -- hold 144 of the 160 KiB) */
-  __shared__ ulonglong2 io[!RGB_TRAIN_RUNS_LDS ? RGB_TICK_BLOCK * RGB_HOT_SLOT
-                           : rgb_class_slice(1, (unsigned)N) == 32u ? 12 * RGB_TICK_BLOCK : 16 * RGB_TICK_BLOCK];
+  __shared__ ulonglong2 io[rgb_class_slice(1, (unsigned)N) == 32u ? 12 * RGB_TICK_BLOCK : 16 * RGB_TICK_BLOCK];
   /* the shard this block serves: the XCD it runs on */
   u32 x;
   {
@@ -3824,7 +3728,7 @@ __device__ __forceinline__ void synth_group(const rgb_dev &dev, u64 seed, u64 ti
     } else if (ld.lwi < ld.li && (r & 3) == 0) {
       const u64 a = ld.lwi + 1 > ld.first ? ld.lwi + 1 : ld.first;
       SynMsg w = syn_msg(sid(l), RGB_MSG_WRITTEN, RGB_NONE, 0, ld.lt, a, ld.li, 0);
-      w.off_steady = RGB_X_HINT && dev.synth_hint >= 1u;   /* the owner is in state leader (ra_server_proc knows) */
+      w.off_steady = dev.synth_hint >= 1u;   /* the owner is in state leader (ra_server_proc knows) */
       emit(w);
     } else if (hb_lag >= 0 && (r >> 40) % 3 == 0) {
       /* a follower that has not confirmed the current query index answers the heartbeat */
@@ -3891,14 +3795,14 @@ __device__ __forceinline__ void synth_group(const rgb_dev &dev, u64 seed, u64 ti
       if (dev.synth_hint >= 2u)
         off = off || f.ct != ld.ct || (unsigned)pk_get(f.pk, PK_LEADER_SH, 4) != (unsigned)l || !(f.first <= f.li) ||
               prev_i != f.li || prev_t != f.lt || (n_ent != 0 && run0 != f.lt);
-      w.off_steady = RGB_X_HINT && dev.synth_hint >= 1u && off;
+      w.off_steady = dev.synth_hint >= 1u && off;
       emit(w);
     } else if (f.lwi < f.li && f.first <= f.li && (r >> 8) % 10 < 8) {
       const u64 a = f.lwi + 1 > f.first ? f.lwi + 1 : f.first;
       SynMsg w = syn_msg(sid(j), RGB_MSG_WRITTEN, RGB_NONE, 0, f.lt, a, f.li, 0);
       bool off = pk_get(f.pk, PK_ROLE_SH, 3) != RGB_ROLE_FOLLOWER;
       if (dev.synth_hint >= 2u) off = off || (unsigned)pk_get(f.pk, PK_LEADER_SH, 4) == SLOT_NONE4;   /* nobody to reply to */
-      w.off_steady = RGB_X_HINT && dev.synth_hint >= 1u && off;
+      w.off_steady = dev.synth_hint >= 1u && off;
       emit(w);
     }
   }
@@ -4249,6 +4153,7 @@ __global__ void rgb_stamp_rounds_kernel(rgb_dev dev, const rgb_msg *__restrict__
  * 3.5 x the decisions' bytes for groups of five, almost all of it empty slots. */
 #define RGB_RES_BLOCK 128u
 #define RGB_RES_MAX_STRIDE 7u       /* rpc slots per message: groups of up to eight members */
+static_assert(RGB_MAX_MEMBERS - 1u <= RGB_RES_MAX_STRIDE, "a message of the largest group has a staging slot for every rpc record");
 __global__ __launch_bounds__(RGB_RES_BLOCK) void rgb_results_sums_kernel(const rgb_decision *__restrict__ dec, const u32 *__restrict__ pos,
                                                                          u32 n, u32 rpc_stride, u32 *__restrict__ block_sums,
                                                                          u32 *__restrict__ err) {
@@ -4277,6 +4182,8 @@ __global__ __launch_bounds__(RGB_RES_BLOCK) void rgb_results_kernel(const ulongl
   __shared__ u64 srec[RGB_RES_BLOCK * RGB_RES_MAX_STRIDE * 7u];                /* 49 KiB */
   __shared__ u32 sscan[RGB_RES_BLOCK];
   __shared__ u32 sred[RGB_RES_BLOCK];
+  static_assert(sizeof(sdec) + sizeof(srec) + sizeof(sscan) + sizeof(sred) <= 64u * 1024u,
+                "the staging arrays fit the 64 KiB a workgroup may allocate statically");
   const u32 tid = threadIdx.x, b = blockIdx.x;
   const u32 i = b * RGB_RES_BLOCK + tid;
   /* the records in front of this block */
@@ -4740,9 +4647,6 @@ u32 rgb_train_resident_blocks(unsigned n_members) {
   }
 #undef LAUNCH
   if (e != hipSuccess || per_cu <= 0) return 0;
-#ifdef RGB_X_TRAIN_GRID_PCT      /* EXPERIMENT: a share of the device's wavefront slots */
-  return (u32)((u64)per_cu * (u32)cus * RGB_X_TRAIN_GRID_PCT / 100u);
-#endif
   return (u32)per_cu * (u32)cus;
 #endif
 }
@@ -4759,9 +4663,6 @@ int rgb_launch_train(const rgb_dev &dev, const rgb_msg *d_msgs, const unsigned c
   if (bpt % RGB_TRAIN_SHARDS || n_ticks > RGB_TRAIN_MAX_TICKS) return -1;
   if (n_xcc == 0 || n_xcc > RGB_TRAIN_SHARDS || (n_xcc & (n_xcc - 1u)) != 0 || n_blocks < RGB_TRAIN_SHARDS) return -1;
   hipStream_t st = (hipStream_t)stream;
-#ifdef RGB_X_PROLOG_FRONT      /* A/B timing only: rounds 3-4 */
-  hipLaunchKernelGGL(rgb_train_prolog_kernel, dim3(1), dim3(256), 0, st, d_ctl, 1u);
-#endif
   /* never more blocks than rows: a block without a row only costs its ticket */
   const uint64_t rows = (uint64_t)n_ticks * bpt;
   dim3 grid((u32)(rows < n_blocks ? rows : n_blocks)), block(RGB_TICK_BLOCK);
@@ -4793,9 +4694,7 @@ int rgb_launch_train(const rgb_dev &dev, const rgb_msg *d_msgs, const unsigned c
    * (d_ctl[0], sticky until it is read) is final when the stream reaches whatever follows -- and every per-launch word
    * (arrival and ticket counters, the marks) is cleared for the next launch on these control words, which a context
    * hands out zeroed */
-#ifndef RGB_X_PROLOG_FRONT
   hipLaunchKernelGGL(rgb_train_prolog_kernel, dim3(1), dim3(256), 0, st, d_ctl, 1u);
-#endif
   return (int)hipGetLastError();
 }
 
