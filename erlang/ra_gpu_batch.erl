@@ -15,7 +15,7 @@
 -module(ra_gpu_batch).
 
 -export([init/0, open/4, register_groups/3, upload_state/3, download_state/3, register_owner/4, unregister_owner/2, owner_slots/1, fan_back_stats/1, route/2,
-         submit/3, submit/4, collect/1, start_collector/2, stop_collector/1, snapshot/2, wal_checksums/3,
+         submit/3, submit/4, submit_raw/4, collect/1, start_collector/2, stop_collector/1, snapshot/2, wal_checksums/3,
          comm_unique_id/0, comm_init/4, allgather_leaderboard/2, node_leaderboard/3]).
 -export([wal_batch_checksums/2, wal_frame/4, wal_recover_check/2, wal_frame_batch/3, wal_recover/2]).
 -export([crc32s/3, crc32_stream/3, segment_build/5, segment_image/4]).
@@ -102,6 +102,13 @@ submit(_Ctx, _MsgsBin, _Tick) -> erlang:nif_error(not_loaded).
 %% submit/4: + the batch's range list, <<First:64/little, Last:64/little>> per entry -- the lower ranges of written
 %% events whose ra_seq has more than two ranges (encode_msgs/2 builds both binaries)
 submit(_Ctx, _MsgsBin, _Tick, _RangesBin) -> erlang:nif_error(not_loaded).
+%% submit_raw/4: the batch travels as it is (one copy into the pinned slot); validation, the sub-tick rounds and the
+%% bucket order run on the device.  MaxRounds = the caller's bound on the messages per server in the batch (1..8,
+%% 0 = 4); a batch may hold at most the largest N with sum_{r < MaxRounds} N div (r + 1) =< RingCapacity messages.
+%% Input errors are the BATCH's result: collect/1 returns {error, invalid | unsupported} once (the collector thread
+%% sends {ra_gpu_batch_error, _} to the default owner), nothing of the batch is applied, the ring moves on.
+%% A dirty IO-bound NIF at every size: the call waits for its turn behind the slots begun before it.
+submit_raw(_Ctx, _MsgsBin, _Tick, _MaxRounds) -> erlang:nif_error(not_loaded).
 collect(_Ctx) -> erlang:nif_error(not_loaded).
 start_collector(_Ctx, _Pid) -> erlang:nif_error(not_loaded).
 stop_collector(_Ctx) -> erlang:nif_error(not_loaded).

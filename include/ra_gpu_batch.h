@@ -464,7 +464,7 @@ enum {
 
 uint32_t    rgb_abi_version(void);
 /* sizeof() of the ABI structs as compiled: 0 rgb_msg, 1 rgb_decision, 2 rgb_rpc,
- * 3 rgb_server_state, 4 rgb_leaderboard_row, 5 rgb_config (bindings verify their mirrors) */
+ * 3 rgb_server_state, 4 rgb_leaderboard_row, 5 rgb_config, 6 rgb_view, 7 rgb_fill (bindings verify their mirrors) */
 size_t      rgb_struct_size(int which);
 const char *rgb_strerror(int code);
 void        rgb_default_config(rgb_config *cfg);
@@ -549,6 +549,44 @@ int      rgb_peek(rgb_ctx *ctx, uint32_t *n_out, uint32_t *n_rpc_out);
 int      rgb_wait(rgb_ctx *ctx, uint32_t timeout_ms);
 void     rgb_wake(rgb_ctx *ctx);
 uint32_t rgb_in_flight(const rgb_ctx *ctx);
+
+/* Submitting without the host passes (new symbols of ABI v10; opt-in, rgb_submit is unchanged).
+ * rgb_submit validates every record, works out the sub-tick rounds and sorts the batch into device order on the
+ * calling thread.  The raw form moves all three to the device (ra_amd/csrc/rgb_prepare.hip): the producer's records
+ * travel in SUBMISSION order and the host checks only the context, the sizes and the slot's state.
+ *   rgb_submit_begin   takes the next ring slot and a ticket (RGB_E_FULL when that slot is not free) and hands out the
+ *                      slot's pinned message buffer: the producer writes out->cap records at most there, in submission
+ *                      order -- the producer-side mirror of rgb_collect_view.  max_rounds = the caller's bound on the
+ *                      messages per server in this batch, 1 .. RGB_SUBMIT_RAW_MAX_ROUNDS, 0 = 4.
+ *   rgb_submit_commit  enqueues the first n records of the slot, in ticket order (it waits for its turn exactly as
+ *                      rgb_submit does).  n = 0 publishes an empty batch: how a producer gives a begun slot back.
+ *                      RGB_E_INVAL for n > cap (the slot stays begun), RGB_E_STATE for a slot that was not begun.
+ *                      A BEGUN SLOT HOLDS UP every later commit and rgb_submit until it is committed: fill promptly.
+ *   rgb_submit_raw     begin, one sequential copy (streaming stores for a batch of 1 MiB and more), commit.
+ * Capacity: the device lays round r out in a region of floor(n / (r + 1)) positions (every server of round r has sent
+ * at least r + 1 messages), so a batch may hold the largest n with  sum over r < max_rounds of floor(n / (r + 1))  <=
+ * ring_capacity: rgb_submit_raw_capacity (ring_capacity for one round, about 0.48 x ring_capacity for four).
+ * Errors of the INPUT are per-batch results: the batch is published, and rgb_collect / rgb_collect_view return the
+ * code ONCE with no decisions (rgb_peek reports the batch as empty), exactly as for a batch whose enqueue failed; the
+ * ring moves on and the batches behind it run normally.  A refused batch applies NOTHING -- no server row changes.
+ *   RGB_E_INVAL        a record that rgb_submit would refuse (kind, server, from, AER run lengths, a written event's
+ *                      ranges), or a written event with RGB_MF_SEQX (the raw form carries no range list)
+ *   RGB_E_UNSUPPORTED  more than max_rounds messages for one server
+ * On a context opened with RGB_CFG_SUBMIT_TRAINS the raw calls run rgb_submit's host passes internally (a train's
+ * undo log needs the list of touched servers, which only the host pass has): rgb_submit_begin hands out a host staging
+ * buffer instead of a ring slot, the ring slot is taken by rgb_submit_commit (which may therefore return RGB_E_FULL,
+ * the slot staying begun), and the results -- per-batch errors included -- are the same. */
+#define RGB_SUBMIT_RAW_MAX_ROUNDS 8u
+typedef struct rgb_fill {
+  rgb_msg *msgs;          /* cap records of pinned memory: write the batch here, submission order */
+  uint32_t cap;           /* = rgb_submit_raw_capacity(ctx, max_rounds) */
+  uint32_t slot;          /* for rgb_submit_commit */
+  uint32_t max_rounds;    /* as resolved (0 -> 4) */
+} rgb_fill;
+uint32_t rgb_submit_raw_capacity(const rgb_ctx *ctx, uint32_t max_rounds);
+int      rgb_submit_begin(rgb_ctx *ctx, uint32_t max_rounds, rgb_fill *out);
+int      rgb_submit_commit(rgb_ctx *ctx, uint32_t slot, uint32_t n, uint64_t tick);
+int      rgb_submit_raw(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint32_t max_rounds, uint64_t tick);
 
 /* Multi-GPU routing below any host language (the group -> node-local shard map that
  * ra_leaderboard / the ra_directory lookup give the reference, src/ra_leaderboard.erl:18-26): the context

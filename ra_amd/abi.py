@@ -168,9 +168,12 @@ SEG_MAX_ENTRIES, SEG_MAX_SIZE_B = 4096, 64_000_000            # src/ra.hrl:225, 
 # rgb_view (ABI v9, rgb_collect_view): pointers into the pinned slot the device wrote
 VIEW_DTYPE = np.dtype([("decisions", "<u8"), ("rpcs", "<u8"), ("tick", "<u8"), ("n", "<u4"), ("n_rpcs", "<u4"),
                        ("slot", "<u4"), ("_pad", "<u4")])
+# rgb_fill (rgb_submit_begin): the slot's pinned message buffer, handed to the producer
+FILL_DTYPE = np.dtype([("msgs", "<u8"), ("cap", "<u4"), ("slot", "<u4"), ("max_rounds", "<u4"), ("_pad", "<u4")])
+SUBMIT_RAW_MAX_ROUNDS = 8
 STRUCT_DTYPES = [MSG_DTYPE, DECISION_DTYPE, RPC_DTYPE, SERVER_STATE_DTYPE, LEADERBOARD_DTYPE,
-                 CONFIG_DTYPE, VIEW_DTYPE]
-EXPECTED_SIZES = [64, 64, 56, 704, 32, 32, 40]
+                 CONFIG_DTYPE, VIEW_DTYPE, FILL_DTYPE]
+EXPECTED_SIZES = [64, 64, 56, 704, 32, 32, 40, 24]
 for _dt, _sz in zip(STRUCT_DTYPES, EXPECTED_SIZES):
     assert _dt.itemsize == _sz, (_dt, _dt.itemsize, _sz)
 

@@ -312,6 +312,24 @@ static ERL_NIF_TERM nif_submit(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
   return submit_body(env, argc, argv);
 }
 
+/* submit_raw(Ctx, <<rgb_msg x N>>, Tick, MaxRounds): rgb_submit_raw -- ONE copy from the binary into the slot's pinned
+ * buffer; validation, the sub-tick rounds and the bucket order run on the device.  What submit/3 answers {error, invalid}
+ * or {error, unsupported} for comes back as the BATCH's result instead: collect/1 returns it once, the collector thread
+ * reports it to the default owner as {ra_gpu_batch_error, _} -- the path of a batch whose enqueue failed.  MaxRounds =
+ * the caller's bound on the messages per server in the batch (1..8, 0 = 4).
+ * A dirty IO-bound NIF at every size (submit/3 goes to a dirty scheduler above SUBMIT_DIRTY_MSGS only): the host work
+ * is one copy, but the call waits for its turn behind every slot that was begun before it, and how long a producer
+ * takes to fill a begun slot is not the library's to bound. */
+static ERL_NIF_TERM nif_submit_raw(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary b; uint64_t tick; unsigned rounds;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &b) || b.size % sizeof(rgb_msg) ||
+      !enif_get_uint64(env, argv[2], &tick) || !enif_get_uint(env, argv[3], &rounds))
+    return enif_make_badarg(env);
+  int rc = rgb_submit_raw(c->ctx, (const rgb_msg *)b.data, (uint32_t)(b.size / sizeof(rgb_msg)), rounds, tick);
+  return rc ? mk_error(env, c, rc) : enif_make_atom(env, "ok");
+}
+
 static int do_collect(nif_ctx *c, ErlNifBinary *dec, ErlNifBinary *rpc, uint32_t *n, uint32_t *nr, uint64_t *tick) {
   /* the binaries are sized from the batch itself (rgb_peek waits for it): exactly byte_size(DecisionsBin) div 64
    * decisions and byte_size(RpcsBin) div 56 rpc records, no ring-capacity-sized allocation per batch */
@@ -727,6 +745,7 @@ static ErlNifFunc nif_funcs[] = {
   {"fan_back_stats", 1, nif_fan_back_stats, 0},
   {"submit", 3, nif_submit, 0},
   {"submit", 4, nif_submit, 0},
+  {"submit_raw", 4, nif_submit_raw, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"collect", 1, nif_collect, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"start_collector", 2, nif_start_collector, 0},
   {"stop_collector", 1, nif_stop_collector, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -115,6 +115,14 @@ struct rgb_slot {
   uint64_t tick = 0;
   hipEvent_t done = nullptr;
   hipEvent_t copied = nullptr;      /* the batch's messages are on the device (recorded on the copy stream) */
+  /* rgb_submit_begin / rgb_submit_commit (a batch the DEVICE puts in order: rgb_prepare.hip) */
+  rgb_msg *d_raw = nullptr;         /* the records as submitted; allocated with the slot's first raw batch */
+  unsigned char *d_key = nullptr;   /* (round, family) of every record */
+  rgb_msg *h_stage = nullptr;       /* RGB_CFG_SUBMIT_TRAINS contexts: the host buffer rgb_submit_begin hands out instead */
+  bool raw = false;                 /* the batch in the slot is a raw one: h_nrpc[3] holds its per-batch code */
+  u32 raw_rounds = 0;
+  uint64_t raw_ticket = 0;
+  std::atomic<int> begun{0};        /* 0 | 1 begun (slot and ticket taken) | 2 begun on a trains context (h_stage only) */
 };
 
 /* Threading contract of the staging ring: any number of threads may call rgb_submit -- they
@@ -189,6 +197,11 @@ struct rgb_ctx {
   std::atomic<bool> train_dealt{false}; /* trains run in the dealt form (one block per row): the calibration launch was dealt
                                            round robin over 8 XCCs and no launch has failed its placement check since */
   int xcc_state = 0;                    /* 0 = not calibrated, 1 = usable, -1 = the XCC ids are not 0 .. n-1 with n | 8 */
+  /* raw batches (rgb_prepare.hip): touched only by kernels on `stream`, so the batches serialise on them.  Allocated
+   * with the context's first raw batch (under submit_mu) */
+  u32 *d_srv_cnt = nullptr;             /* n_servers counters, zero between batches */
+  u32 *d_srv_list = nullptr;            /* n_servers x RGB_PREP_MAX_ROUNDS message indices */
+  u32 *d_prep = nullptr;                /* RGB_PREP_WORDS: error word, (round, family) counts, bucket cursors */
 };
 
 /* the device plan of a train: one rgb_train_tick per tick */
@@ -229,6 +242,7 @@ size_t rgb_struct_size(int which) {
     case 4: return sizeof(rgb_leaderboard_row);
     case 5: return sizeof(rgb_config);
     case 6: return sizeof(rgb_view);
+    case 7: return sizeof(rgb_fill);
     default: return 0;
   }
 }
@@ -301,6 +315,10 @@ static void free_slot(rgb_slot &s) {
   if (s.done) (void)hipEventDestroy(s.done);
   if (s.copied) (void)hipEventDestroy(s.copied);
   s.copied = nullptr;
+  if (s.d_raw) (void)hipFree(s.d_raw);
+  if (s.d_key) (void)hipFree(s.d_key);
+  free(s.h_stage);
+  s.d_raw = nullptr; s.d_key = nullptr; s.h_stage = nullptr;
   s.h_msgs = nullptr; s.h_dec = nullptr; s.d_msgs = nullptr; s.d_dec = nullptr; s.d_rpcs = nullptr; s.h_rpcs = nullptr;
   s.h_nrpc = nullptr; s.d_res = nullptr;
   s.h_stamps = s.d_stamps = nullptr; s.h_plan = s.d_plan = nullptr; s.h_rows = s.d_rows = nullptr; s.done = nullptr;
@@ -334,6 +352,9 @@ void rgb_close(rgb_ctx *ctx) {
   if (ctx->d_synth_sent) (void)hipFree(ctx->d_synth_sent);
   if (ctx->d_train_ctl) (void)hipFree(ctx->d_train_ctl);
   if (ctx->d_seq_cnt) (void)hipFree(ctx->d_seq_cnt);
+  if (ctx->d_srv_cnt) (void)hipFree(ctx->d_srv_cnt);
+  if (ctx->d_srv_list) (void)hipFree(ctx->d_srv_list);
+  if (ctx->d_prep) (void)hipFree(ctx->d_prep);
 
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -1037,10 +1058,14 @@ static int take_oldest(rgb_ctx *ctx, bool have_out, uint32_t cap, bool have_rpc_
     s.used_train = false;
     ctx->trains_in_flight.fetch_sub(1, std::memory_order_release);
   }
+  /* a raw batch the device refused (rgb_prepare.hip left the code in the header): delivered like a failed enqueue.
+   * Looked at first: nothing of such a batch ran, so what the results kernels found at its positions means nothing */
+  if (!fail && s.raw && s.n && s.h_nrpc[3] != 0) fail = -(int)s.h_nrpc[3];
   /* a message reported more records than it has slots (a kind that cannot emit rpcs did): unrecoverable for this
    * batch -- it is consumed all the same, so the ring moves on and the caller sees the error once */
   if (!fail && s.n && s.h_nrpc[2] != 0) fail = RGB_E_STATE;
   if (fail) {
+    s.raw = false; s.h_nrpc[3] = 0;
     if (s.used_train) { s.used_train = false; ctx->trains_in_flight.fetch_sub(1, std::memory_order_release); }
     s.enqueue_error = 0;
     ctx->tail = (ctx->tail + 1) % ctx->ring_size;
@@ -1056,6 +1081,7 @@ static int take_oldest(rgb_ctx *ctx, bool have_out, uint32_t cap, bool have_rpc_
     if (n_rpc_out) *n_rpc_out = n_rpc;
     return (s.n > cap || (s.n && !have_out)) ? RGB_E_INVAL : RGB_E_FULL;
   }
+  s.raw = false;
   s.state.store(3, std::memory_order_relaxed);              /* mine: the next consumer takes the next slot */
   ctx->tail = (ctx->tail + 1) % ctx->ring_size;
   ctx->in_flight.fetch_sub(1, std::memory_order_release);
@@ -1127,9 +1153,204 @@ int rgb_peek(rgb_ctx *ctx, uint32_t *n_out, uint32_t *n_rpc_out) {
     if (rc) return rc;
   }
   const u32 n_rpc = (s.n && !s.enqueue_error) ? s.h_nrpc[0] : 0u;
+  if (s.raw && s.n && s.h_nrpc[3] != 0) return RGB_OK;         /* a refused raw batch hands out nothing: sized as empty */
   if (n_out) *n_out = s.n;
   if (n_rpc_out) *n_rpc_out = n_rpc;
   return RGB_OK;
+}
+
+/* ---- submitting without the host passes (include/ra_gpu_batch.h; the device side is rgb_prepare.hip) ---- */
+static inline u32 raw_rounds_of(uint32_t max_rounds) { return max_rounds ? max_rounds : 4u; }
+
+uint32_t rgb_submit_raw_capacity(const rgb_ctx *ctx, uint32_t max_rounds) {
+  const u32 R = raw_rounds_of(max_rounds);
+  if (!ctx || R > RGB_SUBMIT_RAW_MAX_ROUNDS) return 0;
+  /* the largest n whose round regions fit the slot: rgb_raw_round_base(n, R) is monotone in n */
+  u32 lo = 0, hi = ctx->cfg.ring_capacity;
+  while (lo < hi) {
+    const u32 mid = lo + (hi - lo + 1u) / 2u;
+    if (rgb_raw_round_base(mid, R) <= ctx->cfg.ring_capacity) lo = mid; else hi = mid - 1u;
+  }
+  return lo;
+}
+
+/* the device buffers of the raw form, with the first batch that needs them (caller holds submit_mu) */
+static int raw_scratch(rgb_ctx *ctx, rgb_slot &s) {
+  const size_t S = ctx->dev.n_servers, cap = ctx->cfg.ring_capacity;
+  if (!ctx->d_srv_cnt) {
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_srv_cnt, S * sizeof(u32)));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_srv_cnt, 0, S * sizeof(u32), ctx->stream));
+  }
+  if (!ctx->d_srv_list) HIPCHK(ctx, hipMalloc((void **)&ctx->d_srv_list, S * RGB_PREP_MAX_ROUNDS * sizeof(u32)));
+  if (!ctx->d_prep) HIPCHK(ctx, hipMalloc((void **)&ctx->d_prep, RGB_PREP_WORDS * sizeof(u32)));
+  if (!s.d_raw) HIPCHK(ctx, hipMalloc((void **)&s.d_raw, cap * sizeof(rgb_msg)));
+  if (!s.d_key) HIPCHK(ctx, hipMalloc((void **)&s.d_key, cap));
+  return RGB_OK;
+}
+
+/* what a raw batch puts on the stream (under enqueue_mu, in ticket order): one copy of the records as submitted, the
+ * prepare kernels, one class-dispatch launch per round over the round's fixed region with the device's family totals
+ * (a round the batch does not have finds zeros and returns), the results kernels, the slot's event */
+static int enqueue_raw(rgb_ctx *ctx, rgb_slot &s) {
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  const u32 n = s.n, R = s.raw_rounds;
+  s.h_nrpc[0] = 0; s.h_nrpc[1] = 0; s.h_nrpc[2] = 0; s.h_nrpc[3] = 0;
+  if (!n) { HIPCHK(ctx, hipEventRecord(s.done, ctx->stream)); return RGB_OK; }
+  const size_t bytes = (size_t)n * sizeof(rgb_msg);
+  if (bytes >= RGB_COPY_STREAM_MIN) {
+    HIPCHK(ctx, hipMemcpyAsync(s.d_raw, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+    HIPCHK(ctx, hipEventRecord(s.copied, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(s.d_raw, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  auto fail = [&](int lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; };
+  int lr = rgb_launch_prepare(ctx->dev, s.d_raw, n, R, ctx->d_srv_cnt, ctx->d_srv_list, ctx->d_prep, s.d_key, s.d_msgs,
+                              s.d_dec, s.d_pos, s.h_nrpc + 3, ctx->stream);
+  if (lr) return fail(lr);
+  for (u32 r = 0; r < R; ++r) {
+    const u32 base = rgb_raw_round_base(n, r), bound = n / (r + 1u);
+    if (!bound) break;
+    lr = rgb_launch_tick_classes(ctx->dev, s.d_msgs + base, nullptr, ctx->d_prep + RGB_PREP_COUNTS + r * RGB_N_FAMILIES,
+                                 bound, s.d_dec + base, s.d_rpcs, base, base, ctx->stream);
+    if (lr) return fail(lr);
+  }
+  return enqueue_results(ctx, s);
+}
+
+/* step 3 for a slot whose ticket is `ticket`: wait for the turn, enqueue (unless rc already holds an error), publish
+ * -- as failed if need be: the ticket is honoured whatever happens */
+static int publish_in_turn(rgb_ctx *ctx, rgb_slot &s, uint64_t ticket, int rc) {
+  {
+    std::unique_lock<std::mutex> el(ctx->enqueue_mu);
+    ctx->enqueue_cv.wait(el, [&] { return ctx->enqueue_turn == ticket; });
+    if (rc == RGB_OK) {
+      try { rc = enqueue_raw(ctx, s); } catch (...) { rc = RGB_E_NOMEM; }
+    }
+    if (rc != RGB_OK) {
+      s.enqueue_error = rc; s.n = 0;
+      (void)hipEventRecord(s.done, ctx->stream);
+    }
+    s.state.store(2, std::memory_order_release);
+    ctx->in_flight.fetch_add(1, std::memory_order_release);
+    ctx->enqueue_turn += 1;
+  }
+  ctx->enqueue_cv.notify_all();
+  { std::lock_guard<std::mutex> wl(ctx->wait_mu); }
+  ctx->wait_cv.notify_one();
+  return rc;
+}
+
+/* the next ring slot and a ticket (step 2 of rgb_submit); with_scratch: the slot's raw buffers exist when it is taken */
+static int take_slot(rgb_ctx *ctx, bool with_scratch, rgb_slot **out, uint64_t *ticket) {
+  std::lock_guard<std::mutex> lk(ctx->submit_mu);
+  rgb_slot *sp = &ctx->ring_mem[ctx->head];
+  if (sp->state.load(std::memory_order_acquire) != 0) return RGB_E_FULL;
+  if (with_scratch) {
+    const int rc = raw_scratch(ctx, *sp);
+    if (rc) return rc;                                       /* (nothing was taken) */
+  }
+  int free_state = 0;
+  if (!sp->state.compare_exchange_strong(free_state, 1, std::memory_order_acquire)) return RGB_E_FULL;
+  ctx->head = (ctx->head + 1) % ctx->ring_size;
+  *ticket = ctx->next_ticket++;
+  rgb_slot &s = *sp;
+  s.n = 0; s.n_ranges = 0; s.has_seqx = false; s.used_train = false; s.enqueue_error = 0; s.has_undo = false;
+  s.n_rounds = 0; s.n_touched = 0; s.raw = false;
+  *out = sp;
+  return RGB_OK;
+}
+
+/* a batch that is refused before anything is enqueued, as a per-batch result (the trains fall-back: there the host
+ * passes find what the device finds otherwise) */
+static int publish_refused(rgb_ctx *ctx, int code, uint64_t tick) {
+  rgb_slot *sp; uint64_t ticket;
+  const int rc = take_slot(ctx, false, &sp, &ticket);
+  if (rc) return rc;
+  sp->tick = tick;
+  (void)publish_in_turn(ctx, *sp, ticket, code);
+  return RGB_OK;
+}
+
+int rgb_submit_begin(rgb_ctx *ctx, uint32_t max_rounds, rgb_fill *out) {
+  if (!ctx || !out) return RGB_E_INVAL;
+  memset(out, 0, sizeof *out);
+  const u32 R = raw_rounds_of(max_rounds);
+  if (R > RGB_SUBMIT_RAW_MAX_ROUNDS) return RGB_E_INVAL;
+  if (!ctx->registered) return RGB_E_STATE;
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  const u32 cap = rgb_submit_raw_capacity(ctx, R);
+  if (ctx->cfg.flags & RGB_CFG_SUBMIT_TRAINS) {
+    /* a host staging buffer, no ring slot yet: rgb_submit_commit runs rgb_submit over it */
+    for (u32 k = 0; k < ctx->ring_size; ++k) {
+      rgb_slot &s = ctx->ring_mem[k];
+      int idle = 0;
+      if (!s.begun.compare_exchange_strong(idle, 2, std::memory_order_acquire)) continue;
+      if (!s.h_stage) s.h_stage = (rgb_msg *)malloc((size_t)ctx->cfg.ring_capacity * sizeof(rgb_msg));
+      if (!s.h_stage) { s.begun.store(0, std::memory_order_release); return RGB_E_NOMEM; }
+      s.raw_rounds = R;
+      out->msgs = s.h_stage; out->cap = cap; out->slot = k; out->max_rounds = R;
+      return RGB_OK;
+    }
+    return RGB_E_FULL;
+  }
+  rgb_slot *sp; uint64_t ticket;
+  const int rc = take_slot(ctx, true, &sp, &ticket);
+  if (rc) return rc;
+  sp->raw = true; sp->raw_rounds = R; sp->raw_ticket = ticket;
+  sp->begun.store(1, std::memory_order_release);
+  out->msgs = sp->h_msgs; out->cap = cap; out->slot = (uint32_t)(sp - ctx->ring_mem.get()); out->max_rounds = R;
+  return RGB_OK;
+}
+
+int rgb_submit_commit(rgb_ctx *ctx, uint32_t slot, uint32_t n, uint64_t tick) {
+  if (!ctx || slot >= ctx->ring_size) return RGB_E_INVAL;
+  rgb_slot &s = ctx->ring_mem[slot];
+  const int begun = s.begun.load(std::memory_order_acquire);
+  if (begun == 0) return RGB_E_STATE;
+  if (n > rgb_submit_raw_capacity(ctx, s.raw_rounds)) return RGB_E_INVAL;
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  if (begun == 2) {
+    const int rc = rgb_submit_raw(ctx, s.h_stage, n, s.raw_rounds, tick);
+    if (rc != RGB_E_FULL) s.begun.store(0, std::memory_order_release);   /* (a full ring: the caller commits again) */
+    return rc;
+  }
+  s.n = n; s.tick = tick;
+  /* the positions lie behind the LAST record the slot can hold: the round regions of n records reach past the n-th */
+  s.h_pos = reinterpret_cast<u32 *>(s.h_msgs + ctx->cfg.ring_capacity);
+  s.d_pos = reinterpret_cast<u32 *>(s.d_msgs + ctx->cfg.ring_capacity);
+  s.begun.store(0, std::memory_order_release);
+  return publish_in_turn(ctx, s, s.raw_ticket, RGB_OK);
+}
+
+int rgb_submit_raw(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint32_t max_rounds, uint64_t tick) {
+  if (!ctx || (!msgs && n)) return RGB_E_INVAL;
+  const u32 R = raw_rounds_of(max_rounds);
+  if (R > RGB_SUBMIT_RAW_MAX_ROUNDS) return RGB_E_INVAL;
+  if (!ctx->registered) return RGB_E_STATE;
+  if (n > rgb_submit_raw_capacity(ctx, R)) return RGB_E_INVAL;
+  if (ctx->cfg.flags & RGB_CFG_SUBMIT_TRAINS) {
+    /* today's host passes; what they refuse because of the input becomes the batch's result, as on the device */
+    thread_local std::vector<unsigned char> seen;
+    if (seen.size() < ctx->dev.n_servers) seen.assign(ctx->dev.n_servers, 0);
+    bool too_many = false;
+    for (u32 i = 0; i < n; ++i)
+      if (msgs[i].kind != RGB_MSG_NOP && msgs[i].server < ctx->dev.n_servers && ++seen[msgs[i].server] > R) too_many = true;
+    for (u32 i = 0; i < n; ++i)
+      if (msgs[i].server < ctx->dev.n_servers) seen[msgs[i].server] = 0;
+    bool seqx = false;
+    for (u32 i = 0; i < n && !seqx; ++i) seqx = msgs[i].kind == RGB_MSG_WRITTEN && (msgs[i].flags & RGB_MF_SEQX);
+    int rc = RGB_OK;
+    for (u32 i = 0; i < n && rc == RGB_OK; ++i) rc = validate_msg(ctx, msgs[i]);
+    if (rc != RGB_OK || seqx) return publish_refused(ctx, RGB_E_INVAL, tick);
+    if (too_many) return publish_refused(ctx, RGB_E_UNSUPPORTED, tick);
+    return rgb_submit_seq(ctx, msgs, n, tick, nullptr, 0);
+  }
+  rgb_fill f;
+  const int rc = rgb_submit_begin(ctx, R, &f);
+  if (rc) return rc;
+  if (n) copy_out(f.msgs, msgs, (size_t)n * sizeof(rgb_msg));
+  return rgb_submit_commit(ctx, f.slot, n, tick);
 }
 
 /* Park until a batch is in flight (RGB_OK), the timeout passes or rgb_wake is called (RGB_E_EMPTY). */
@@ -1788,3 +2009,8 @@ int rgb_synchronize(rgb_ctx *ctx) {
 }
 
 }  /* extern "C" */
+
+/* the emulated library (tests/native) builds this file as one unit with the prepare kernels */
+#ifdef RGB_HOST_EMULATION
+#include "rgb_prepare.hip"
+#endif

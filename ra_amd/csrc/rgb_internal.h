@@ -313,4 +313,31 @@ int rgb_launch_results(const rgb_decision *d_dec, const u32 *d_pos, u32 n, u32 c
 u32 rgb_undo_pieces(const rgb_dev &dev);
 int rgb_launch_undo(const rgb_dev &dev, const u32 *d_ids, u32 n, void *d_undo, u32 restore, void *stream);
 
+/* ---- rgb_prepare.hip: a raw batch (rgb_submit_raw / rgb_submit_commit) put into device order by the device ----
+ * Round r of a batch of n messages owns the positions [rgb_raw_round_base(n, r), + n / (r + 1)): every server of round
+ * r has sent at least r + 1 messages, so the bound holds whatever the batch, and the host knows every base. */
+#define RGB_PREP_MAX_ROUNDS 8u
+static_assert(RGB_PREP_MAX_ROUNDS == RGB_SUBMIT_RAW_MAX_ROUNDS, "a server's message list holds the public bound");
+static inline __host__ __device__ u32 rgb_raw_round_base(u32 n, u32 r) {
+  u32 b = 0;
+  for (u32 q = 0; q < r; ++q) b += n / (q + 1u);
+  return b;
+}
+/* d_prep, per context (the batches serialise on the context's stream): word 0 the batch's error bits, then the
+ * (round, family) counts -- round r's 32 family totals are what its rgb_launch_tick_classes reads -- and the bucket
+ * cursors of the scatter */
+#define RGB_PREP_ERR        0u
+#define RGB_PREP_ERR_INVAL  1u      /* a record validate_msg refuses, or a written event with RGB_MF_SEQX */
+#define RGB_PREP_ERR_ROUNDS 2u      /* more than max_rounds messages for one server */
+#define RGB_PREP_COUNTS     32u
+#define RGB_PREP_CURSORS    (RGB_PREP_COUNTS + RGB_PREP_MAX_ROUNDS * RGB_N_FAMILIES)
+#define RGB_PREP_WORDS      (RGB_PREP_CURSORS + RGB_PREP_MAX_ROUNDS * RGB_N_FAMILIES)
+/* validate + rounds + bucket order of the n records d_raw (submission order): d_msgs in device order, d_pos[i] = the
+ * position of record i, the empty decisions of NOP records in d_dec, the counts in d_prep; *code_out (the slot's pinned
+ * header) = 0 or -RGB_E_* of a refused batch, which moves nothing.  d_srv_cnt: n_servers words, ZERO when allocated
+ * and left zero; d_srv_list: n_servers x RGB_PREP_MAX_ROUNDS words; d_key: one byte per record */
+int rgb_launch_prepare(const rgb_dev &dev, const rgb_msg *d_raw, u32 n, u32 max_rounds, u32 *d_srv_cnt, u32 *d_srv_list,
+                       u32 *d_prep, unsigned char *d_key, rgb_msg *d_msgs, rgb_decision *d_dec, u32 *d_pos,
+                       u32 *code_out, void *stream);
+
 #endif

@@ -28,6 +28,7 @@ EXPORTS = [
     "rgb_train_plan_create_snap", "rgb_train_run_snap_device", "rgb_snapshot_train_device", "rgb_train_seq_bytes",
     "rgb_train_plan_create_device", "rgb_train_plan_build_device", "rgb_train_plan_download", "rgb_train_plan_fit",
     "rgb_submit_seq", "rgb_set_seq_ranges_device", "rgb_collect_view", "rgb_release",
+    "rgb_submit_raw_capacity", "rgb_submit_begin", "rgb_submit_commit", "rgb_submit_raw",
 ]
 COMM_EXPORTS = ["rgb_comm_unique_id", "rgb_comm_init_rank", "rgb_comm_destroy", "rgb_comm_n_ranks", "rgb_comm_rank",
                 "rgb_leaderboard_allgather", "rgb_leaderboard_allgather_host", "rgb_comm_last_error"]   # the one collective of the path (RCCL)
@@ -40,7 +41,8 @@ OPTIONAL_IN_OLD_BUILDS = {"rgb_synth_tick_stamped_device", "rgb_synth_stamps_res
                           "rgb_snapshot_train_device", "rgb_train_seq_bytes", "rgb_synth_snapshot_mark_device",
                           "rgb_synth_set_hint", "rgb_train_plan_create_device", "rgb_train_plan_build_device",
                           "rgb_train_plan_download", "rgb_train_plan_fit", "rgb_submit_seq", "rgb_set_seq_ranges_device",
-                          "rgb_collect_view", "rgb_release"} | set(COMM_EXPORTS)
+                          "rgb_collect_view", "rgb_release", "rgb_submit_raw_capacity", "rgb_submit_begin",
+                          "rgb_submit_commit", "rgb_submit_raw"} | set(COMM_EXPORTS)
 WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "rgb_wal_frame_device",
                "rgb_wal_frame", "rgb_wal_scan", "rgb_wal_validate",
                "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
@@ -55,7 +57,7 @@ class RgbError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("rgb_kernels.hip", "rgb_api.hip", "rgb_wal.hip", "rgb_wal_host.cpp", "rgb_segment.hip",
+    srcs = [os.path.join(_CSRC, f) for f in ("rgb_kernels.hip", "rgb_api.hip", "rgb_prepare.hip", "rgb_wal.hip", "rgb_wal_host.cpp", "rgb_segment.hip",
                                               "rgb_segment_host.cpp", "rgb_comm.cpp", "rgb_internal.h")]
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "ra_gpu_wal.h"))
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "ra_gpu_batch.h"))
@@ -116,6 +118,12 @@ def lib():
     if hasattr(L, "rgb_collect_view"):
         L.rgb_collect_view.argtypes = [vp, vp]
         L.rgb_release.argtypes = [vp, u32]
+    if hasattr(L, "rgb_submit_raw"):
+        L.rgb_submit_raw_capacity.restype = C.c_uint32
+        L.rgb_submit_raw_capacity.argtypes = [vp, u32]
+        L.rgb_submit_begin.argtypes = [vp, u32, vp]
+        L.rgb_submit_commit.argtypes = [vp, u32, u32, C.c_uint64]
+        L.rgb_submit_raw.argtypes = [vp, vp, u32, u32, C.c_uint64]
     L.rgb_run_ticks_device.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp]
     L.rgb_snapshot.argtypes = [vp, vp]
     L.rgb_snapshot_device.argtypes = [vp, vp, vp]
@@ -204,6 +212,8 @@ def lib():
     for i, dt in enumerate(abi.STRUCT_DTYPES):
         if os.environ.get("RGB_LIB") and i >= 6 and L.rgb_abi_version() < abi.ABI_VERSION:
             continue                                       # (an older A/B build has no rgb_view)
+        if os.environ.get("RGB_LIB") and i >= 7 and not hasattr(L, "rgb_submit_raw"):
+            continue                                       # (.. and the build before the raw submit has no rgb_fill)
         if L.rgb_struct_size(i) != dt.itemsize:
             raise RuntimeError(f"struct {i}: C size {L.rgb_struct_size(i)} != numpy {dt.itemsize}")
     _lib = L
@@ -335,6 +345,45 @@ class RaGpuBatch:
 
     def release(self, slot: int):
         self._check(self._L.rgb_release(self._h, slot), "rgb_release")
+
+    # -- submitting without the host passes: validation, rounds and bucket order on the device --------
+    def raw_capacity(self, max_rounds: int = 4) -> int:
+        """Messages a raw batch may hold when no server gets more than max_rounds of them (rgb_submit_raw_capacity)."""
+        return int(self._L.rgb_submit_raw_capacity(self._h, max_rounds))
+
+    def submit_raw(self, msgs: np.ndarray, tick: int = 0, max_rounds: int = 4):
+        """rgb_submit_raw: the records travel in submission order; what rgb_submit refuses synchronously because of
+        the input comes back from collect() / collect_view() instead, once, as the batch's error."""
+        m = np.ascontiguousarray(msgs, dtype=abi.MSG_DTYPE)
+        self._check(self._L.rgb_submit_raw(self._h, m.ctypes.data, len(m), max_rounds, tick), "rgb_submit_raw")
+
+    def submit_begin(self, max_rounds: int = 4):
+        """rgb_submit_begin: (records, slot) -- a numpy view of the slot's pinned message buffer (raw_capacity(max_rounds)
+        records) to fill in submission order, and the slot for submit_commit.  Every later commit and submit waits
+        for this slot's commit."""
+        f = np.zeros(1, dtype=abi.FILL_DTYPE)
+        self._check(self._L.rgb_submit_begin(self._h, max_rounds, f.ctypes.data), "rgb_submit_begin")
+        cap = int(f["cap"][0])
+        buf = (C.c_char * (max(cap, 1) * abi.MSG_DTYPE.itemsize)).from_address(int(f["msgs"][0]))
+        return np.frombuffer(buf, dtype=abi.MSG_DTYPE, count=cap), int(f["slot"][0])
+
+    def submit_commit(self, slot: int, n: int, tick: int = 0):
+        self._check(self._L.rgb_submit_commit(self._h, slot, n, tick), "rgb_submit_commit")
+
+    def step_raw(self, msgs: np.ndarray, max_rounds: int = 4):
+        """submit_raw + collect, in chunks of raw_capacity(max_rounds)."""
+        m = np.ascontiguousarray(msgs, dtype=abi.MSG_DTYPE)
+        cap = self.raw_capacity(max_rounds)
+        out_d, out_r = [], []
+        for off in range(0, max(len(m), 1), cap):
+            chunk = m[off:off + cap]
+            self.submit_raw(chunk, max_rounds=max_rounds)
+            d, r, _ = self.collect(cap=max(len(chunk), 1))
+            r = r.copy()
+            r["msg_index"] += off
+            out_d.append(d)
+            out_r.append(r)
+        return np.concatenate(out_d), np.concatenate(out_r)
 
     def wait(self, timeout_ms: int = 1000) -> bool:
         """Park until a batch is in flight (True) or the timeout / a wake() passes (False)."""
