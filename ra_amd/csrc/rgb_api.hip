@@ -1,11 +1,15 @@
 /*
  * rgb_api.hip -- the C ABI of include/ra_gpu_batch.h on top of the HIP kernels.
  *
- * Host path (what the Erlang NIF drives): rgb_submit copies the caller's messages into a
- * slot of a pinned staging ring, then enqueues  H2D -> transition kernel(s) -> D2H  on the
- * context's stream and returns; rgb_collect waits on the slot's event and hands decisions back
- * in submission order.  Messages addressed to the same server inside one batch are serialised
- * into sub-ticks (round r holds every server's r-th message), one kernel launch per round.
+ * Host path (what the Erlang NIF drives): rgb_submit sorts the caller's messages into a slot of a pinned staging
+ * ring -- by sub-tick round (round r holds every server's r-th message of the batch), then by clause family -- and
+ * enqueues on the context's stream: one copy to the device, the rounds (one class-dispatch launch per round, or all
+ * rounds as ONE train launch), the results kernels, the slot's event.  Nothing is copied back: the results kernels
+ * write the decisions (submission order) and the compacted rpc records into the pinned slot.  rgb_collect waits on
+ * the slot's event and hands them out, oldest batch first.  The raw form (rgb_submit_raw, rgb_submit_begin /
+ * rgb_submit_commit) sends the records as submitted: validation, rounds and bucket order run on the device
+ * (rgb_prepare.hip) and an input error comes back as the batch's result.  Both forms share one producer protocol:
+ * take_slot (a ring slot and a ticket), publish_in_turn (the stream's work and the publication, in ticket order).
  *
  * There is no CPU fallback: without a HIP device rgb_open fails with RGB_E_NODEVICE.
  */
@@ -76,6 +80,15 @@ static inline void copy_out(void *dst, const void *src, size_t bytes) {
       return RGB_E_HIP;                            \
     }                                              \
   } while (0)
+/* the same for the internal launchers (rgb_internal.h): they return 0 or the hipError_t of their launch as an int */
+#define LAUNCHCHK(ctx, expr)                       \
+  do {                                             \
+    int lr__ = (expr);                             \
+    if (lr__) {                                    \
+      (ctx)->last_hip.store(lr__, std::memory_order_relaxed); \
+      return RGB_E_HIP;                            \
+    }                                              \
+  } while (0)
 
 struct rgb_slot {
   rgb_msg *h_msgs = nullptr;        /* pinned: the batch in device order, then h_pos -- ONE copy to the device */
@@ -124,6 +137,10 @@ struct rgb_slot {
   uint64_t raw_ticket = 0;
   std::atomic<int> begun{0};        /* 0 | 1 begun (slot and ticket taken) | 2 begun on a trains context (h_stage only) */
 };
+/* what the header of a batch whose event has completed says: its train launch failed (the error word came back with
+ * the results); the device refused it (a raw batch: rgb_prepare.hip left the code there) */
+static inline bool train_failed(const rgb_slot &s) { return s.used_train && !s.enqueue_error && s.h_nrpc[1] != 0; }
+static inline bool raw_refused(const rgb_slot &s) { return s.raw && s.n && s.h_nrpc[3] != 0; }
 
 /* Threading contract of the staging ring: any number of threads may call rgb_submit -- they
  * prepare their batches in parallel (validation, rounds, the bucket sort into the slot's pinned buffer) and meet in
@@ -216,15 +233,6 @@ struct rgb_train_plan {
   std::vector<u32> rows_fit;  /* on_device: the rows of every tick the host has been TOLD (rgb_train_plan_fit), else
                                  0xFFFFFFFF: a launch whose ticks are all known takes their rows as its grid, not the bound */
 };
-
-/* A tick ordered by clause family: ONE launch of the class-dispatch kernel. */
-static int launch_tick_classes(rgb_ctx *ctx, const rgb_dev &dev, const rgb_msg *m, rgb_decision *d, rgb_rpc *rpcs,
-                               const u32 counts[RGB_N_CLASSES], u32 rpc_slot_base, u32 msg_index_base,
-                               hipStream_t main) {
-  int rc = rgb_launch_tick_classes(dev, m, counts, nullptr, 0, d, rpcs, rpc_slot_base, msg_index_base, main);
-  if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
-  return RGB_OK;
-}
 
 extern "C" void rgb_wal_release(rgb_ctx *ctx);   /* rgb_wal.hip: staging buffers of the host-buffer form */
 extern "C" void rgb_seg_release(rgb_ctx *ctx);   /* rgb_segment.hip: the same for the segment / snapshot part */
@@ -549,8 +557,7 @@ int rgb_upload_state(rgb_ctx *ctx, uint32_t first, uint32_t n, const rgb_server_
     memcpy(ctx->h_stage, in + base, (size_t)cnt * sizeof(rgb_server_state));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage, ctx->h_stage, (size_t)cnt * sizeof(rgb_server_state),
                                hipMemcpyHostToDevice, ctx->stream));
-    int rc = rgb_launch_pack(ctx->dev, ctx->d_stage, first + base, cnt, ctx->stream);
-    if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_pack(ctx->dev, ctx->d_stage, first + base, cnt, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   return RGB_OK;
@@ -565,8 +572,7 @@ int rgb_download_state(rgb_ctx *ctx, uint32_t first, uint32_t n, rgb_server_stat
   if (turn.rc) return turn.rc;
   for (u32 base = 0; base < n; base += ctx->stage_cap) {
     u32 cnt = n - base < ctx->stage_cap ? n - base : ctx->stage_cap;
-    int rc = rgb_launch_unpack(ctx->dev, ctx->d_stage, first + base, cnt, ctx->stream);
-    if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_unpack(ctx->dev, ctx->d_stage, first + base, cnt, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_stage, (size_t)cnt * sizeof(rgb_server_state),
                                hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -607,8 +613,6 @@ static int train_scratch(rgb_ctx *ctx);
 #define RGB_FAULT_STAMP 1u   /* its first message carries a stamp that never comes up: RGB_TRAIN_ERR_SPIN            */
 #define RGB_FAULT_SHARD 2u   /* two messages of one class and round swap shards: RGB_TRAIN_ERR_PLACEMENT            */
 
-/* the rounds of a batch with one launch per round (the shape of every batch that is not a train, and the replay of
- * one whose train launch failed) */
 /* the device view of one batch: the context's, plus the batch's own range list */
 static rgb_dev slot_dev(const rgb_ctx *ctx, const rgb_slot &s) {
   rgb_dev d = ctx->dev;
@@ -617,9 +621,14 @@ static rgb_dev slot_dev(const rgb_ctx *ctx, const rgb_slot &s) {
   return d;
 }
 
+/* the rounds of a batch with one launch per round (the shape of every batch that is not a train, and the replay of
+ * one whose train launch failed) */
 static int enqueue_rounds(rgb_ctx *ctx, rgb_slot &s) {
   const rgb_dev dv = slot_dev(ctx, s);
-  auto fail = [&](int lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; };
+  /* a part of a round ordered by clause family: ONE launch of the class-dispatch kernel */
+  auto classes = [&](const u32 counts[RGB_N_CLASSES], u32 at) {
+    return rgb_launch_tick_classes(dv, s.d_msgs + at, counts, nullptr, 0, s.d_dec + at, s.d_rpcs, at, at, ctx->stream);
+  };
   for (u32 r = 0; r < s.n_rounds; ++r) {
     const u32 off = s.round_start[r], cnt = s.round_start[r + 1] - s.round_start[r];
     /* every round, whatever its size, runs the class-dispatch kernel -- a path specialised per message kind, no
@@ -631,10 +640,8 @@ static int enqueue_rounds(rgb_ctx *ctx, rgb_slot &s) {
       real += cc[c];
       if (c < 2) before_written += cc[c];
     }
-    int lr;
     if (!s.has_seqx || cc[2] == 0) {
-      lr = launch_tick_classes(ctx, dv, s.d_msgs + off, s.d_dec + off, s.d_rpcs, cc, off, off, ctx->stream);
-      if (lr) return lr;
+      LAUNCHCHK(ctx, classes(cc, off));
     } else {
       /* a batch of rgb_submit_seq: its written events may carry range lists (RGB_MF_SEQX), which the class kernel's
        * written path does not take -- the classes in front of the written class, the written class through the
@@ -643,23 +650,14 @@ static int enqueue_rounds(rgb_ctx *ctx, rgb_slot &s) {
       u32 head[RGB_N_CLASSES] = {0}, tail[RGB_N_CLASSES] = {0};
       head[0] = cc[0]; head[1] = cc[1];
       for (int c = 3; c < RGB_N_CLASSES; ++c) tail[c] = cc[c];
-      if (before_written) {
-        lr = launch_tick_classes(ctx, dv, s.d_msgs + off, s.d_dec + off, s.d_rpcs, head, off, off, ctx->stream);
-        if (lr) return lr;
-      }
+      if (before_written) LAUNCHCHK(ctx, classes(head, off));
       const u32 w0 = off + before_written, t0 = w0 + cc[2];
-      lr = rgb_launch_tick(dv, RGB_TICK_CLS_WRITTEN_SEQX, s.d_msgs + w0, cc[2], nullptr, s.d_dec + w0, s.d_rpcs, w0, w0, ctx->stream);
-      if (lr) return fail(lr);
-      if (real > before_written + cc[2]) {
-        lr = launch_tick_classes(ctx, dv, s.d_msgs + t0, s.d_dec + t0, s.d_rpcs, tail, t0, t0, ctx->stream);
-        if (lr) return lr;
-      }
+      LAUNCHCHK(ctx, rgb_launch_tick(dv, RGB_TICK_CLS_WRITTEN_SEQX, s.d_msgs + w0, cc[2], nullptr, s.d_dec + w0, s.d_rpcs, w0, w0, ctx->stream));
+      if (real > before_written + cc[2]) LAUNCHCHK(ctx, classes(tail, t0));
     }
-    if (real < cnt) {      /* NOP slots sort last: their empty decisions */
-      lr = rgb_launch_tick(dv, RGB_TICK_CLS_NOP, s.d_msgs + off + real, cnt - real, nullptr, s.d_dec + off + real,
-                           s.d_rpcs, off + real, off + real, ctx->stream);
-      if (lr) return fail(lr);
-    }
+    if (real < cnt)        /* NOP slots sort last: their empty decisions */
+      LAUNCHCHK(ctx, rgb_launch_tick(dv, RGB_TICK_CLS_NOP, s.d_msgs + off + real, cnt - real, nullptr, s.d_dec + off + real,
+                                     s.d_rpcs, off + real, off + real, ctx->stream));
   }
   return RGB_OK;
 }
@@ -668,11 +666,46 @@ static int enqueue_rounds(rgb_ctx *ctx, rgb_slot &s) {
  * decisions in submission order, the rpc records compacted, the header (records, a train's error word -- the launch's
  * placement marks went into it: rgb_launch_train); then the slot's event */
 static int enqueue_results(rgb_ctx *ctx, rgb_slot &s) {
-  int lr = rgb_launch_results(s.d_dec, s.d_pos, s.n, ctx->cfg.ring_capacity, s.d_rpcs, ctx->rpc_stride, s.d_res, s.used_train ? s.d_ctl : nullptr,
-                              s.h_dec, s.h_rpcs, s.h_nrpc, ctx->stream);
-  if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_results(s.d_dec, s.d_pos, s.n, ctx->cfg.ring_capacity, s.d_rpcs, ctx->rpc_stride, s.d_res, s.used_train ? s.d_ctl : nullptr,
+                                    s.h_dec, s.h_rpcs, s.h_nrpc, ctx->stream));
   HIPCHK(ctx, hipEventRecord(s.done, ctx->stream));
   return RGB_OK;
+}
+
+/* a batch's copy to the device (`bytes` of the slot's pinned buffer): a big one on the copy stream, the decision
+ * stream waiting for its event; a small one on the decision stream itself (RGB_COPY_STREAM_MIN).  The slot's device
+ * buffers are free: its previous batch was collected, i.e. its event had completed */
+static int enqueue_copy_in(rgb_ctx *ctx, rgb_slot &s, void *dst, size_t bytes) {
+  if (bytes >= RGB_COPY_STREAM_MIN) {
+    HIPCHK(ctx, hipMemcpyAsync(dst, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+    HIPCHK(ctx, hipEventRecord(s.copied, ctx->copy_stream));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(dst, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return RGB_OK;
+}
+
+/* TEST SUPPORT (rgb_debug_inject_train_fault; the fail-safe tests): the fault waiting in the context, if any, is
+ * applied to this train batch, in the slot's pinned buffers, before they are copied */
+static void apply_injected_fault(rgb_ctx *ctx, rgb_slot &s) {
+  const u32 fault = ctx->inject_fault.exchange(0u, std::memory_order_relaxed);
+  if (fault == RGB_FAULT_STAMP) s.h_stamps[0] = (unsigned char)(s.h_stamps[0] + 7u);   /* (round + 7: never comes up) */
+  if (fault != RGB_FAULT_SHARD) return;
+  /* the first messages of two shards of one (round, class) change places (with their stamps and their places in
+   * the permutation): the tick is still class-ordered, so the per-round replay computes it */
+  const rgb_train_tick &t0 = s.h_plan[0];
+  for (u32 c = 0; c < RGB_N_PCLASSES; ++c)
+    for (u32 x = 0; x + 1 < RGB_TRAIN_SHARDS; ++x) {
+      if (t0.cnt[c][x] == 0 || t0.cnt[c][x + 1] == 0) continue;
+      const u32 a = t0.msg_base + t0.off[c][x], b = t0.msg_base + t0.off[c][x + 1];
+      std::swap(s.h_msgs[a], s.h_msgs[b]); std::swap(s.h_stamps[a], s.h_stamps[b]);
+      for (u32 i = 0; i < s.n; ++i) {                         /* (the submitted messages that sit at a and b) */
+        if (s.h_pos[i] == a) s.h_pos[i] = b;
+        else if (s.h_pos[i] == b) s.h_pos[i] = a;
+      }
+      return;
+    }
 }
 
 /* step 3 of rgb_submit (under enqueue_mu, in ticket order): everything the batch puts on the stream */
@@ -681,39 +714,9 @@ static int enqueue_batch(rgb_ctx *ctx, rgb_slot &s, bool as_train, u32 rows_max)
   const u32 n = s.n;
   s.h_nrpc[0] = 0; s.h_nrpc[1] = 0; s.h_nrpc[2] = 0;
   if (!n) { HIPCHK(ctx, hipEventRecord(s.done, ctx->stream)); return RGB_OK; }
-  u32 fault = 0;
-  if (as_train) {
-    fault = ctx->inject_fault.exchange(0u, std::memory_order_relaxed);
-    if (fault == RGB_FAULT_STAMP) s.h_stamps[0] = (unsigned char)(s.h_stamps[0] + 7u);   /* (round + 7: never comes up) */
-    if (fault == RGB_FAULT_SHARD) {
-      /* the first messages of two shards of one (round, class) change places (with their stamps and their places in
-       * the permutation): the tick is still class-ordered, so the per-round replay computes it */
-      bool done = false;
-      for (u32 c = 0; c < RGB_N_PCLASSES && !done; ++c)
-        for (u32 x = 0; x + 1 < RGB_TRAIN_SHARDS && !done; ++x) {
-          const rgb_train_tick &t0 = s.h_plan[0];
-          if (t0.cnt[c][x] == 0 || t0.cnt[c][x + 1] == 0) continue;
-          const u32 a = t0.msg_base + t0.off[c][x], b = t0.msg_base + t0.off[c][x + 1];
-          std::swap(s.h_msgs[a], s.h_msgs[b]); std::swap(s.h_stamps[a], s.h_stamps[b]);
-          for (u32 i = 0; i < n; ++i) {                       /* (the submitted messages that sit at a and b) */
-            if (s.h_pos[i] == a) s.h_pos[i] = b;
-            else if (s.h_pos[i] == b) s.h_pos[i] = a;
-          }
-          done = true;
-        }
-    }
-  }
-  {
-    const size_t bytes = (size_t)n * (sizeof(rgb_msg) + sizeof(u32));                               /* messages + h_pos */
-    if (bytes >= RGB_COPY_STREAM_MIN) {
-      /* (the slot's device buffers are free: its previous batch was collected, i.e. its event had completed) */
-      HIPCHK(ctx, hipMemcpyAsync(s.d_msgs, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-      HIPCHK(ctx, hipEventRecord(s.copied, ctx->copy_stream));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
-    } else {
-      HIPCHK(ctx, hipMemcpyAsync(s.d_msgs, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-  }
+  if (as_train) apply_injected_fault(ctx, s);
+  int rc = enqueue_copy_in(ctx, s, s.d_msgs, (size_t)n * (sizeof(rgb_msg) + sizeof(u32)));          /* messages + h_pos */
+  if (rc) return rc;
   if (s.n_ranges)
     HIPCHK(ctx, hipMemcpyAsync(s.d_ranges, s.h_ranges, (size_t)s.n_ranges * 2u * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
   /* the undo log: the rows of the touched servers as they are before this batch -- while a train is in flight
@@ -725,32 +728,27 @@ static int enqueue_batch(rgb_ctx *ctx, rgb_slot &s, bool as_train, u32 rows_max)
         HIPCHK(ctx, hipMalloc(&s.d_undo, servers * rgb_undo_pieces(ctx->dev) * 16u));
       }
       HIPCHK(ctx, hipMemcpyAsync(s.d_touched, s.h_touched, (size_t)s.n_touched * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-      int lr = rgb_launch_undo(ctx->dev, s.d_touched, s.n_touched, s.d_undo, 0, ctx->stream);
-      if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+      LAUNCHCHK(ctx, rgb_launch_undo(ctx->dev, s.d_touched, s.n_touched, s.d_undo, 0, ctx->stream));
     }
     s.has_undo = true;
   }
   if (as_train) {
     HIPCHK(ctx, hipMemcpyAsync(s.d_stamps, s.h_stamps, n, hipMemcpyHostToDevice, ctx->stream));
-    {
-      int lr = rgb_launch_stamp_rounds(ctx->dev, s.d_msgs, n, s.d_stamps, ctx->stream);
-      if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
-    }
+    LAUNCHCHK(ctx, rgb_launch_stamp_rounds(ctx->dev, s.d_msgs, n, s.d_stamps, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(s.d_plan, s.h_plan, (size_t)s.n_rounds * sizeof(rgb_train_tick), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(s.d_rows, s.h_rows, (size_t)s.n_rounds * rows_max * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(s.d_ctl, 0, sizeof(u32), ctx->stream));    /* this slot's own error word */
-    int lr = rgb_launch_train(slot_dev(ctx, s), s.d_msgs, s.d_stamps, 0, s.d_plan, s.d_rows, s.n_rounds, rows_max * RGB_TRAIN_SHARDS,
-                              s.d_dec, s.d_rpcs, 1, 0, s.d_ctl, ctx->n_xcc,
-                              ctx->train_dealt.load(std::memory_order_relaxed) ? 0u : ctx->train_blocks, ctx->stream);
-    if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_train(slot_dev(ctx, s), s.d_msgs, s.d_stamps, 0, s.d_plan, s.d_rows, s.n_rounds, rows_max * RGB_TRAIN_SHARDS,
+                                    s.d_dec, s.d_rpcs, 1, 0, s.d_ctl, ctx->n_xcc,
+                                    ctx->train_dealt.load(std::memory_order_relaxed) ? 0u : ctx->train_blocks, ctx->stream));
     s.used_train = true;
     ctx->trains_in_flight.fetch_add(1, std::memory_order_release);
     ctx->n_submit_trains.fetch_add(1, std::memory_order_relaxed);
   } else {
-    int rc = enqueue_rounds(ctx, s);
+    rc = enqueue_rounds(ctx, s);
     if (rc) return rc;
   }
-  int rc = enqueue_results(ctx, s);
+  rc = enqueue_results(ctx, s);
   if (rc && s.used_train) { s.used_train = false; ctx->trains_in_flight.fetch_sub(1, std::memory_order_release); }
   return rc;
 }
@@ -758,7 +756,17 @@ static int enqueue_batch(rgb_ctx *ctx, rgb_slot &s, bool as_train, u32 rows_max)
 /* pass 1 of rgb_submit, compiled per group size: the bucket key holds the server's shard = (server / n_members) mod 8,
  * a division by a constant here (a multiply) instead of one by a run-time value per message; the per-thread scratch
  * comes in as plain pointers (a thread_local std::vector is reached through its guard function at every use) */
-struct submit_scan { u32 n_rounds = 0; bool any_nop = false, too_many = false, any_seqx = false; int bad = RGB_OK; };
+struct submit_scan {
+  u32 n_rounds = 0; bool any_nop = false, too_many = false, any_seqx = false; int bad = RGB_OK;
+  /* .. and the rest of what step 1 of rgb_submit hands to steps 2 and 3 (submit_prepare) */
+  bool as_train = false;
+  u32 NK = 0;                       /* buckets per round: RGB_N_BUCKETS for a train, else RGB_N_FAMILIES */
+  u32 rows_max = 0;                 /* a train: the rows of its longest round (fill_slot) */
+  const u32 *round_of = nullptr;    /* the calling thread's scratch: valid until its next submit */
+  const uint16_t *key_of = nullptr;
+  const std::vector<u32> *touched = nullptr;
+  std::vector<u32> start, bucket, bucket_counts, class_counts;
+};
 extern "C++" {
 template <unsigned NM>
 static void submit_pass1(const rgb_ctx *ctx, const rgb_msg *msgs, u32 n, const uint64_t *ranges, uint32_t n_ranges,
@@ -791,11 +799,12 @@ static void submit_pass1(const rgb_ctx *ctx, const rgb_msg *msgs, u32 n, const u
  * round r = tick r of the train, every round in bucket order, the per-server sequence bytes order a server's
  * messages instead of a kernel boundary per round. */
 /* rgb_submit in three steps, so that any number of producers prepare their batches IN PARALLEL:
- *   1. no lock: validation, the sub-tick rounds (thread-local scratch), the bucket counts;
- *   2. submit_mu, O(1): take the next ring slot and a ticket -- RGB_E_FULL when that slot is not free;
- *      then, no lock: the bucket sort of the batch into the slot's pinned buffer, the train plan;
- *   3. enqueue_mu, in ticket order: the stream's work (H2D, kernels, D2H, event), the train stamps (they count on from
- *      the previous batch), publication.  Batches reach the device in the order their submits took their slots.
+ *   1. submit_prepare, no lock: validation, the sub-tick rounds (thread-local scratch), the bucket counts;
+ *   2. take_slot, submit_mu, O(1): the next ring slot and a ticket -- RGB_E_FULL when that slot is not free;
+ *      then fill_slot, no lock: the bucket sort of the batch into the slot's pinned buffer, the train plan;
+ *   3. publish_in_turn, enqueue_mu, in ticket order: the stream's work (enqueue_batch: the copy in, the kernels, the
+ *      event; the train stamps count on from the previous batch), publication.  Batches reach the device in the order
+ *      their submits took their slots.
  * Everything that can fail because of the INPUT fails before step 2; a HIP error in step 3 publishes the batch as
  * failed (rgb_collect returns the error once and the ring moves on). */
 int rgb_submit(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick) {
@@ -811,15 +820,78 @@ int rgb_set_seq_ranges_device(rgb_ctx *ctx, const void *d_ranges, uint32_t n_ran
   return RGB_OK;
 }
 
-int rgb_submit_seq(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick, const uint64_t *ranges, uint32_t n_ranges) {
-  if (!ctx || (!msgs && n) || (!ranges && n_ranges)) return RGB_E_INVAL;
-  if (!ctx->registered) return RGB_E_STATE;
-  if (n > ctx->cfg.ring_capacity) return RGB_E_INVAL;
-  /* the calling thread's current device may be any (one context per GPU, scheduler threads default to device 0):
-   * everything below -- the one-off train calibration included -- runs on the context's */
-  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  /* ---- 1. ONE pass over the batch: validation, the rounds (round r = every server's r-th message of this batch,
-   * in order; per-thread scratch) and every message's bucket key -- the later passes read 6 bytes per message, not 64 */
+/* the device buffers of the raw form, with the first batch that needs them (caller holds submit_mu) */
+static int raw_scratch(rgb_ctx *ctx, rgb_slot &s) {
+  const size_t S = ctx->dev.n_servers, cap = ctx->cfg.ring_capacity;
+  if (!ctx->d_srv_cnt) {
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_srv_cnt, S * sizeof(u32)));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_srv_cnt, 0, S * sizeof(u32), ctx->stream));
+  }
+  if (!ctx->d_srv_list) HIPCHK(ctx, hipMalloc((void **)&ctx->d_srv_list, S * RGB_PREP_MAX_ROUNDS * sizeof(u32)));
+  if (!ctx->d_prep) HIPCHK(ctx, hipMalloc((void **)&ctx->d_prep, RGB_PREP_WORDS * sizeof(u32)));
+  if (!s.d_raw) HIPCHK(ctx, hipMalloc((void **)&s.d_raw, cap * sizeof(rgb_msg)));
+  if (!s.d_key) HIPCHK(ctx, hipMalloc((void **)&s.d_key, cap));
+  return RGB_OK;
+}
+
+/* ---- the producer protocol of the staging ring, for every form of submit ---- */
+/* step 2: the next ring slot and a ticket -- RGB_E_FULL when that slot is not free; with_scratch: the slot's raw
+ * buffers exist when it is taken.  An error takes nothing.  From a ticket on, nothing returns early and whatever throws
+ * is caught: the ticket must be honoured by publish_in_turn (enqueue_turn advances, the slot is published -- as failed
+ * if need be) or every later submit would block for ever */
+static int take_slot(rgb_ctx *ctx, bool with_scratch, rgb_slot **out, uint64_t *ticket) {
+  std::lock_guard<std::mutex> lk(ctx->submit_mu);
+  rgb_slot *sp = &ctx->ring_mem[ctx->head];
+  if (sp->state.load(std::memory_order_acquire) != 0) return RGB_E_FULL;
+  if (with_scratch) {
+    const int rc = raw_scratch(ctx, *sp);
+    if (rc) return rc;                                       /* (nothing was taken) */
+  }
+  int free_state = 0;
+  /* acquire: a slot a consumer gave back (release store in rgb_collect) is really free */
+  if (!sp->state.compare_exchange_strong(free_state, 1, std::memory_order_acquire)) return RGB_E_FULL;
+  ctx->head = (ctx->head + 1) % ctx->ring_size;
+  *ticket = ctx->next_ticket++;
+  rgb_slot &s = *sp;
+  s.n = 0; s.n_ranges = 0; s.has_seqx = false; s.used_train = false; s.enqueue_error = 0; s.has_undo = false;
+  s.n_rounds = 0; s.n_touched = 0; s.raw = false;
+  *out = sp;
+  return RGB_OK;
+}
+
+/* step 3 for a slot whose ticket is `ticket`: wait for the turn, put the batch's work on the stream (`enqueue`, unless
+ * rc already holds an error), publish -- as failed if need be: rgb_collect reports the error once and the ring moves on */
+extern "C++" {
+template <typename Enqueue>
+static int publish_in_turn(rgb_ctx *ctx, rgb_slot &s, uint64_t ticket, int rc, Enqueue enqueue) {
+  {
+    std::unique_lock<std::mutex> el(ctx->enqueue_mu);
+    ctx->enqueue_cv.wait(el, [&] { return ctx->enqueue_turn == ticket; });
+    if (rc == RGB_OK) {
+      try { rc = enqueue(); } catch (...) { rc = RGB_E_NOMEM; }
+    }
+    if (rc != RGB_OK) {
+      s.enqueue_error = rc; s.n = 0; s.used_train = false; s.has_undo = false;
+      (void)hipEventRecord(s.done, ctx->stream);
+    }
+    /* publish: everything written to the slot above happens-before the consumer's acquire load */
+    s.state.store(2, std::memory_order_release);
+    ctx->in_flight.fetch_add(1, std::memory_order_release);
+    ctx->enqueue_turn += 1;
+  }
+  ctx->enqueue_cv.notify_all();
+  { std::lock_guard<std::mutex> wl(ctx->wait_mu); }
+  ctx->wait_cv.notify_one();
+  return rc;
+}
+}  // extern "C++"
+
+/* step 1 of rgb_submit (no lock): ONE pass over the batch -- validation, the rounds (round r = every server's r-th
+ * message of this batch, in order; per-thread scratch) and every message's bucket key: the later passes read 6 bytes
+ * per message, not 64 --, then the train decision and the bucket and class counts.  Returns the INPUT's error (more
+ * than max_rounds messages for one server is one) before anything else is looked at */
+static int submit_prepare(rgb_ctx *ctx, const rgb_msg *msgs, u32 n, const uint64_t *ranges, uint32_t n_ranges, u32 max_rounds,
+                          submit_scan &sc) {
   thread_local std::vector<uint16_t> seen, key_of;
   thread_local std::vector<u32> touched, round_of;
   if (seen.size() < ctx->dev.n_servers) seen.assign(ctx->dev.n_servers, 0);
@@ -827,24 +899,20 @@ int rgb_submit_seq(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick,
   key_of.resize(n);
   touched.clear();
   if (touched.capacity() < n) touched.reserve(n);
-  const unsigned n_members = ctx->dev.n_members;
-  submit_scan sc;
   sc.n_rounds = n ? 1 : 0;
-  switch (n_members) {
+  switch (ctx->dev.n_members) {
 #define RGB_SCAN_N(NM) case NM: submit_pass1<NM>(ctx, msgs, n, ranges, n_ranges, seen.data(), key_of.data(), round_of.data(), touched, sc); break;
     RGB_SCAN_N(1) RGB_SCAN_N(2) RGB_SCAN_N(3) RGB_SCAN_N(4) RGB_SCAN_N(5) RGB_SCAN_N(6) RGB_SCAN_N(7) RGB_SCAN_N(8)
 #undef RGB_SCAN_N
     default: return RGB_E_STATE;
   }
-  u32 n_rounds = sc.n_rounds;
-  const bool any_nop = sc.any_nop, too_many = sc.too_many, any_seqx = sc.any_seqx;
-  const int bad = sc.bad;
   for (u32 t : touched) seen[t] = 0;
-  if (bad) return bad;
-  if (too_many) return RGB_E_UNSUPPORTED;
+  if (sc.bad) return sc.bad;
+  if (sc.too_many || sc.n_rounds > max_rounds) return RGB_E_UNSUPPORTED;
+  const u32 n_rounds = sc.n_rounds;
   /* several rounds, a batch worth a big launch, no NOP padding, a device that keeps a shard on one XCD: the rounds
    * run as ONE train launch, in bucket order (class, shard, success flag) -- a finer key of the same family order */
-  bool as_train = n_rounds >= 2 && n_rounds <= RGB_SUBMIT_TRAIN_ROUNDS && n >= RGB_SUBMIT_TRAIN_MIN && !any_nop && !any_seqx &&
+  bool as_train = n_rounds >= 2 && n_rounds <= RGB_SUBMIT_TRAIN_ROUNDS && n >= RGB_SUBMIT_TRAIN_MIN && !sc.any_nop && !sc.any_seqx &&
                   (ctx->cfg.flags & RGB_CFG_SUBMIT_TRAINS) && !(ctx->cfg.flags & RGB_CFG_ROUNDS_PER_LAUNCH);
   if (as_train) {
     std::lock_guard<std::mutex> tl(ctx->train_mu);          /* the one-off calibration uses the stream */
@@ -853,7 +921,7 @@ int rgb_submit_seq(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick,
     if (!as_train && getenv("RGB_TRACE_TRAIN_SETUP"))
       fprintf(stderr, "[rgb] rgb_submit: no train (setup rc %d, hip %d)\n", ts, ctx->last_hip.load());
   } else if (getenv("RGB_TRACE_TRAIN_SETUP")) {
-    fprintf(stderr, "[rgb] rgb_submit: n %u rounds %u nop %d -> launch per round\n", n, n_rounds, (int)any_nop);
+    fprintf(stderr, "[rgb] rgb_submit: n %u rounds %u nop %d -> launch per round\n", n, n_rounds, (int)sc.any_nop);
   }
   /* device order: by round, then by clause family = (message kind, success flag) (a round holds
    * at most one message per server, so its order is free; family-homogeneous wavefronts do not
@@ -861,9 +929,9 @@ int rgb_submit_seq(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick,
   const u32 NK = as_train ? (u32)RGB_N_BUCKETS : (u32)RGB_N_FAMILIES;
   /* the family (kind rank, success flag) is the bucket key without its shard bits */
   auto family = [as_train](uint16_t key) -> u32 { return as_train ? (u32)key : (((u32)key >> 4) << 1) | ((u32)key & 1u); };
-  std::vector<u32> bucket_counts;
-  std::vector<u32> start(n_rounds + 1, 0);
-  std::vector<u32> bucket((size_t)n_rounds * NK + 1, 0);
+  std::vector<u32> &start = sc.start, &bucket = sc.bucket, &class_counts = sc.class_counts;
+  start.assign(n_rounds + 1, 0);
+  bucket.assign((size_t)n_rounds * NK + 1, 0);
   const u32 *const ro = round_of.data();                 /* (plain pointers: see submit_pass1) */
   const uint16_t *const ko = key_of.data();
   /* (runs of one bucket -- a mailbox drain is clustered by kind -- are counted in a register: an increment per
@@ -882,116 +950,111 @@ int rgb_submit_seq(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick,
     for (u32 k = 0; k < NK; ++k) t += bucket[(size_t)r * NK + k + 1];
     start[r + 1] = start[r] + t;
   }
-  if (as_train) bucket_counts.assign(bucket.begin() + 1, bucket.end());      /* per (round, bucket), before the scan */
+  if (as_train) sc.bucket_counts.assign(bucket.begin() + 1, bucket.end());   /* per (round, bucket), before the scan */
   for (size_t b = 0; b < (size_t)n_rounds * NK; ++b) bucket[b + 1] += bucket[b];
 
   /* per round: the class sizes (what one launch per round needs -- the fall-back of a train and its replay after a
    * failed launch) and the span of device positions whose kind can emit rpc records.  A bucket holds one class, so
-   * both follow from the bucket bounds (bucket[b] .. bucket[b + 1] before the scatter below moves them) */
-  std::vector<u32> class_counts((size_t)n_rounds * RGB_N_CLASSES, 0);
+   * both follow from the bucket bounds (bucket[b] .. bucket[b + 1] before the scatter of step 2 moves them) */
+  class_counts.assign((size_t)n_rounds * RGB_N_CLASSES, 0);
   for (size_t b = 0; b < (size_t)n_rounds * NK; ++b) {
     const u32 b0 = bucket[b], b1 = bucket[b + 1];
     if (b1 == b0) continue;
     const u32 cls = (u32)(b % NK) / (as_train ? 2u * RGB_TRAIN_SHARDS : 2u);      /* kind rank; 15 = NOP */
     if (cls < RGB_N_CLASSES) class_counts[(b / NK) * RGB_N_CLASSES + cls] += b1 - b0;
   }
-  /* ---- 2. the slot and the ticket.  From here to the publication nothing returns early and whatever throws is
-   * caught: the ticket must be honoured (enqueue_turn advances, the slot is published -- as failed if need be) or
-   * every later rgb_submit would block for ever ---- */
-  rgb_slot *sp;
-  uint64_t ticket;
-  {
-    std::lock_guard<std::mutex> lk(ctx->submit_mu);
-    sp = &ctx->ring_mem[ctx->head];
-    int free_state = 0;
-    /* acquire: a slot a consumer gave back (release store in rgb_collect) is really free */
-    if (!sp->state.compare_exchange_strong(free_state, 1, std::memory_order_acquire)) return RGB_E_FULL;
-    ctx->head = (ctx->head + 1) % ctx->ring_size;
-    ticket = ctx->next_ticket++;
-  }
-  rgb_slot &s = *sp;
-  int rc = RGB_OK;
-  u32 rows_max = 0;
-  try {
-    s.h_pos = reinterpret_cast<u32 *>(s.h_msgs + n); s.d_pos = reinterpret_cast<u32 *>(s.d_msgs + n);
-    const bool stream_copy = (size_t)n * sizeof(rgb_msg) >= RGB_STREAM_COPY_MIN;
-    {
-      size_t cur = (size_t)-1; u32 next = 0;                  /* (the current bucket's cursor lives in a register) */
-      for (u32 i = 0; i < n; ++i) {
-        const size_t b = (size_t)ro[i] * NK + family(ko[i]);
-        if (b != cur) { if (cur != (size_t)-1) bucket[cur] = next; cur = b; next = bucket[b]; }
-        const u32 p = next++;
-        s.h_pos[i] = p;
-        copy_msg(&s.h_msgs[p], &msgs[i], stream_copy);
-        if (as_train) s.h_stamps[p] = (unsigned char)ro[i];   /* a train's stamps: the device adds the sequence bytes */
-      }
-      if (cur != (size_t)-1) bucket[cur] = next;
-    }
-#if defined(__x86_64__)
-    if (stream_copy) _mm_sfence();                        /* (the streaming stores are ordered before the copy command) */
-#endif
-    s.n = n; s.tick = tick;
-    s.n_ranges = 0; s.has_seqx = any_seqx;
-    if (n_ranges) {                                            /* the batch's range list travels with it */
-      if (s.ranges_cap < n_ranges) {
-        if (s.h_ranges) (void)hipHostFree(s.h_ranges);
-        if (s.d_ranges) (void)hipFree(s.d_ranges);
-        s.h_ranges = s.d_ranges = nullptr; s.ranges_cap = 0;
-        const u32 cap = n_ranges < 1024u ? 1024u : n_ranges;
-        if (hipHostMalloc((void **)&s.h_ranges, (size_t)cap * 2u * sizeof(u64), hipHostMallocDefault) != hipSuccess ||
-            hipMalloc((void **)&s.d_ranges, (size_t)cap * 2u * sizeof(u64)) != hipSuccess) {
-          rc = RGB_E_NOMEM;
-        } else s.ranges_cap = cap;
-      }
-      if (rc == RGB_OK) { memcpy(s.h_ranges, ranges, (size_t)n_ranges * 2u * sizeof(u64)); s.n_ranges = n_ranges; }
-    }
-    s.used_train = false; s.enqueue_error = 0; s.has_undo = false;
-    s.n_rounds = n_rounds;
-    s.round_start.swap(start);                                  /* no allocation: the vectors change hands */
-    s.round_cc.swap(class_counts);
-    s.n_touched = (u32)touched.size();
-    if (s.n_touched) memcpy(s.h_touched, touched.data(), (size_t)s.n_touched * sizeof(u32));
-    if (as_train) {                                            /* the plan of every round: slot-local, no lock */
-      for (u32 r = 0; r < n_rounds; ++r) {
-        const u32 rows = rgb_train_make_tick(bucket_counts.data() + (size_t)r * RGB_N_BUCKETS, n_members, &s.h_plan[r], nullptr, 0);
-        if (rows > rows_max) rows_max = rows;
-      }
-      if (rows_max == 0 || rows_max > s.rows_cap) as_train = false;   /* more rows than the slot's table holds */
-      for (u32 r = 0; as_train && r < n_rounds; ++r) {
-        for (u32 k = 0; k < rows_max; ++k) s.h_rows[(size_t)r * rows_max + k] = 0xFFFFFFFFu;
-        rgb_train_make_tick(bucket_counts.data() + (size_t)r * RGB_N_BUCKETS, n_members, &s.h_plan[r], s.h_rows + (size_t)r * rows_max, rows_max);
-        s.h_plan[r].msg_base = s.round_start[r];
-      }
-    }
-  } catch (...) {
-    rc = RGB_E_NOMEM;
-  }
+  sc.as_train = as_train; sc.NK = NK;
+  sc.round_of = ro; sc.key_of = ko; sc.touched = &touched;
+  return RGB_OK;
+}
 
-  /* ---- 3. the stream's work, in ticket order ---- */
+/* step 2 behind take_slot (no lock: the slot is this producer's): the bucket sort of the batch into the slot's pinned
+ * buffer, its range list, the touched list, the train plan */
+static int fill_slot(rgb_ctx *ctx, rgb_slot &s, const rgb_msg *msgs, u32 n, uint64_t tick, const uint64_t *ranges,
+                     uint32_t n_ranges, submit_scan &sc) {
+  const bool fine = sc.as_train;                           /* (bucket keys with their shard bits: submit_prepare) */
+  const u32 NK = sc.NK, n_rounds = sc.n_rounds;
+  auto family = [fine](uint16_t key) -> u32 { return fine ? (u32)key : (((u32)key >> 4) << 1) | ((u32)key & 1u); };
+  const u32 *const ro = sc.round_of;
+  const uint16_t *const ko = sc.key_of;
+  std::vector<u32> &bucket = sc.bucket;
+  s.h_pos = reinterpret_cast<u32 *>(s.h_msgs + n); s.d_pos = reinterpret_cast<u32 *>(s.d_msgs + n);
+  const bool stream_copy = (size_t)n * sizeof(rgb_msg) >= RGB_STREAM_COPY_MIN;
   {
-    std::unique_lock<std::mutex> el(ctx->enqueue_mu);
-    ctx->enqueue_cv.wait(el, [&] { return ctx->enqueue_turn == ticket; });
-    if (rc == RGB_OK) {
-      try {
-        rc = enqueue_batch(ctx, s, as_train, rows_max);
-      } catch (...) {
-        rc = RGB_E_NOMEM;
-      }
+    size_t cur = (size_t)-1; u32 next = 0;                  /* (the current bucket's cursor lives in a register) */
+    for (u32 i = 0; i < n; ++i) {
+      const size_t b = (size_t)ro[i] * NK + family(ko[i]);
+      if (b != cur) { if (cur != (size_t)-1) bucket[cur] = next; cur = b; next = bucket[b]; }
+      const u32 p = next++;
+      s.h_pos[i] = p;
+      copy_msg(&s.h_msgs[p], &msgs[i], stream_copy);
+      if (fine) s.h_stamps[p] = (unsigned char)ro[i];       /* a train's stamps: the device adds the sequence bytes */
     }
-    if (rc != RGB_OK) {
-      /* published as failed: rgb_collect reports the error once and the ring moves on */
-      s.enqueue_error = rc; s.n = 0; s.used_train = false; s.has_undo = false;
-      (void)hipEventRecord(s.done, ctx->stream);
-    }
-    /* publish: everything written to the slot above happens-before the consumer's acquire load */
-    s.state.store(2, std::memory_order_release);
-    ctx->in_flight.fetch_add(1, std::memory_order_release);
-    ctx->enqueue_turn += 1;
+    if (cur != (size_t)-1) bucket[cur] = next;
   }
-  ctx->enqueue_cv.notify_all();
-  { std::lock_guard<std::mutex> wl(ctx->wait_mu); }
-  ctx->wait_cv.notify_one();
-  return rc;
+#if defined(__x86_64__)
+  if (stream_copy) _mm_sfence();                          /* (the streaming stores are ordered before the copy command) */
+#endif
+  s.n = n; s.tick = tick;
+  s.has_seqx = sc.any_seqx;
+  if (n_ranges) {                                            /* the batch's range list travels with it */
+    if (s.ranges_cap < n_ranges) {
+      if (s.h_ranges) (void)hipHostFree(s.h_ranges);
+      if (s.d_ranges) (void)hipFree(s.d_ranges);
+      s.h_ranges = s.d_ranges = nullptr; s.ranges_cap = 0;
+      const u32 cap = n_ranges < 1024u ? 1024u : n_ranges;
+      if (hipHostMalloc((void **)&s.h_ranges, (size_t)cap * 2u * sizeof(u64), hipHostMallocDefault) != hipSuccess ||
+          hipMalloc((void **)&s.d_ranges, (size_t)cap * 2u * sizeof(u64)) != hipSuccess)
+        return RGB_E_NOMEM;
+      s.ranges_cap = cap;
+    }
+    memcpy(s.h_ranges, ranges, (size_t)n_ranges * 2u * sizeof(u64));
+    s.n_ranges = n_ranges;
+  }
+  s.n_rounds = n_rounds;
+  s.round_start.swap(sc.start);                               /* no allocation: the vectors change hands */
+  s.round_cc.swap(sc.class_counts);
+  s.n_touched = (u32)sc.touched->size();
+  if (s.n_touched) memcpy(s.h_touched, sc.touched->data(), (size_t)s.n_touched * sizeof(u32));
+  if (sc.as_train) {                                         /* the plan of every round: slot-local, no lock */
+    const unsigned n_members = ctx->dev.n_members;
+    u32 rows_max = 0;
+    for (u32 r = 0; r < n_rounds; ++r) {
+      const u32 rows = rgb_train_make_tick(sc.bucket_counts.data() + (size_t)r * RGB_N_BUCKETS, n_members, &s.h_plan[r], nullptr, 0);
+      if (rows > rows_max) rows_max = rows;
+    }
+    if (rows_max == 0 || rows_max > s.rows_cap) sc.as_train = false;   /* more rows than the slot's table holds */
+    for (u32 r = 0; sc.as_train && r < n_rounds; ++r) {
+      for (u32 k = 0; k < rows_max; ++k) s.h_rows[(size_t)r * rows_max + k] = 0xFFFFFFFFu;
+      rgb_train_make_tick(sc.bucket_counts.data() + (size_t)r * RGB_N_BUCKETS, n_members, &s.h_plan[r], s.h_rows + (size_t)r * rows_max, rows_max);
+      s.h_plan[r].msg_base = s.round_start[r];
+    }
+    sc.rows_max = rows_max;
+  }
+  return RGB_OK;
+}
+
+/* steps 2 and 3 for a batch that passed step 1 */
+static int submit_prepared(rgb_ctx *ctx, const rgb_msg *msgs, u32 n, uint64_t tick, const uint64_t *ranges, uint32_t n_ranges,
+                           submit_scan &sc) {
+  rgb_slot *sp; uint64_t ticket;
+  int rc = take_slot(ctx, false, &sp, &ticket);
+  if (rc) return rc;
+  rgb_slot &s = *sp;
+  try { rc = fill_slot(ctx, s, msgs, n, tick, ranges, n_ranges, sc); } catch (...) { rc = RGB_E_NOMEM; }
+  return publish_in_turn(ctx, s, ticket, rc, [&] { return enqueue_batch(ctx, s, sc.as_train, sc.rows_max); });
+}
+
+int rgb_submit_seq(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint64_t tick, const uint64_t *ranges, uint32_t n_ranges) {
+  if (!ctx || (!msgs && n) || (!ranges && n_ranges)) return RGB_E_INVAL;
+  if (!ctx->registered) return RGB_E_STATE;
+  if (n > ctx->cfg.ring_capacity) return RGB_E_INVAL;
+  /* the calling thread's current device may be any (one context per GPU, scheduler threads default to device 0):
+   * everything below -- the one-off train calibration included -- runs on the context's */
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  submit_scan sc;
+  const int bad = submit_prepare(ctx, msgs, n, ranges, n_ranges, 0xFFFFFFFFu, sc);   /* (rounds: as many as the batch has) */
+  return bad ? bad : submit_prepared(ctx, msgs, n, tick, ranges, n_ranges, sc);
 }
 
 /* A train launch that failed (RGB_TRAIN_ERR_*: a dependency that never committed, a tick out of bucket order) has
@@ -1010,7 +1073,7 @@ static int settle_trains(rgb_ctx *ctx) {
     const u32 j = (ctx->tail + k) % ctx->ring_size;
     rgb_slot &s = ctx->ring_mem[j];
     if (s.state.load(std::memory_order_acquire) != 2) break;
-    if (first_bad == 0xFFFFFFFFu && s.used_train && !s.enqueue_error && s.h_nrpc[1] != 0) first_bad = m;
+    if (first_bad == 0xFFFFFFFFu && train_failed(s)) first_bad = m;
     idx[m++] = j;
   }
   if (first_bad == 0xFFFFFFFFu) return RGB_OK;
@@ -1021,8 +1084,7 @@ static int settle_trains(rgb_ctx *ctx) {
     rgb_slot &s = ctx->ring_mem[idx[k]];
     if (s.enqueue_error || !s.n) continue;
     if (!s.has_undo) return RGB_E_STATE;                    /* cannot happen: enqueued behind a train in flight */
-    int lr = rgb_launch_undo(ctx->dev, s.d_touched, s.n_touched, s.d_undo, 1, ctx->stream);
-    if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_undo(ctx->dev, s.d_touched, s.n_touched, s.d_undo, 1, ctx->stream));
   }
   for (u32 k = first_bad; k < m; ++k) {
     rgb_slot &s = ctx->ring_mem[idx[k]];
@@ -1048,9 +1110,8 @@ static int take_oldest(rgb_ctx *ctx, bool have_out, uint32_t cap, bool have_rpc_
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
   HIPCHK(ctx, hipEventSynchronize(s.done));
   int fail = s.enqueue_error;
-  if (!fail && s.used_train && s.h_nrpc[1] != 0) {
-    /* the train launch of this batch failed (its error word came back with the results): repair the device
-     * state and run this batch and everything enqueued behind it again, one launch per round */
+  if (train_failed(s)) {
+    /* repair the device state and run this batch and everything enqueued behind it again, one launch per round */
     std::lock_guard<std::mutex> el(ctx->enqueue_mu);
     fail = settle_trains(ctx);
   }
@@ -1058,9 +1119,9 @@ static int take_oldest(rgb_ctx *ctx, bool have_out, uint32_t cap, bool have_rpc_
     s.used_train = false;
     ctx->trains_in_flight.fetch_sub(1, std::memory_order_release);
   }
-  /* a raw batch the device refused (rgb_prepare.hip left the code in the header): delivered like a failed enqueue.
-   * Looked at first: nothing of such a batch ran, so what the results kernels found at its positions means nothing */
-  if (!fail && s.raw && s.n && s.h_nrpc[3] != 0) fail = -(int)s.h_nrpc[3];
+  /* a raw batch the device refused: delivered like a failed enqueue.  Looked at first: nothing of such a batch ran,
+   * so what the results kernels found at its positions means nothing */
+  if (!fail && raw_refused(s)) fail = -(int)s.h_nrpc[3];
   /* a message reported more records than it has slots (a kind that cannot emit rpcs did): unrecoverable for this
    * batch -- it is consumed all the same, so the ring moves on and the caller sees the error once */
   if (!fail && s.n && s.h_nrpc[2] != 0) fail = RGB_E_STATE;
@@ -1147,13 +1208,13 @@ int rgb_peek(rgb_ctx *ctx, uint32_t *n_out, uint32_t *n_rpc_out) {
   rgb_slot &s = ctx->ring_mem[ctx->tail];
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
   HIPCHK(ctx, hipEventSynchronize(s.done));
-  if (!s.enqueue_error && s.used_train && s.h_nrpc[1] != 0) {   /* a failed train launch: repaired before it is sized */
+  if (train_failed(s)) {                                       /* repaired before it is sized */
     std::lock_guard<std::mutex> el(ctx->enqueue_mu);
     int rc = settle_trains(ctx);
     if (rc) return rc;
   }
   const u32 n_rpc = (s.n && !s.enqueue_error) ? s.h_nrpc[0] : 0u;
-  if (s.raw && s.n && s.h_nrpc[3] != 0) return RGB_OK;         /* a refused raw batch hands out nothing: sized as empty */
+  if (raw_refused(s)) return RGB_OK;                           /* it hands out nothing: sized as empty */
   if (n_out) *n_out = s.n;
   if (n_rpc_out) *n_rpc_out = n_rpc;
   return RGB_OK;
@@ -1174,20 +1235,6 @@ uint32_t rgb_submit_raw_capacity(const rgb_ctx *ctx, uint32_t max_rounds) {
   return lo;
 }
 
-/* the device buffers of the raw form, with the first batch that needs them (caller holds submit_mu) */
-static int raw_scratch(rgb_ctx *ctx, rgb_slot &s) {
-  const size_t S = ctx->dev.n_servers, cap = ctx->cfg.ring_capacity;
-  if (!ctx->d_srv_cnt) {
-    HIPCHK(ctx, hipMalloc((void **)&ctx->d_srv_cnt, S * sizeof(u32)));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_srv_cnt, 0, S * sizeof(u32), ctx->stream));
-  }
-  if (!ctx->d_srv_list) HIPCHK(ctx, hipMalloc((void **)&ctx->d_srv_list, S * RGB_PREP_MAX_ROUNDS * sizeof(u32)));
-  if (!ctx->d_prep) HIPCHK(ctx, hipMalloc((void **)&ctx->d_prep, RGB_PREP_WORDS * sizeof(u32)));
-  if (!s.d_raw) HIPCHK(ctx, hipMalloc((void **)&s.d_raw, cap * sizeof(rgb_msg)));
-  if (!s.d_key) HIPCHK(ctx, hipMalloc((void **)&s.d_key, cap));
-  return RGB_OK;
-}
-
 /* what a raw batch puts on the stream (under enqueue_mu, in ticket order): one copy of the records as submitted, the
  * prepare kernels, one class-dispatch launch per round over the round's fixed region with the device's family totals
  * (a round the batch does not have finds zeros and returns), the results kernels, the slot's event */
@@ -1196,69 +1243,17 @@ static int enqueue_raw(rgb_ctx *ctx, rgb_slot &s) {
   const u32 n = s.n, R = s.raw_rounds;
   s.h_nrpc[0] = 0; s.h_nrpc[1] = 0; s.h_nrpc[2] = 0; s.h_nrpc[3] = 0;
   if (!n) { HIPCHK(ctx, hipEventRecord(s.done, ctx->stream)); return RGB_OK; }
-  const size_t bytes = (size_t)n * sizeof(rgb_msg);
-  if (bytes >= RGB_COPY_STREAM_MIN) {
-    HIPCHK(ctx, hipMemcpyAsync(s.d_raw, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIPCHK(ctx, hipEventRecord(s.copied, ctx->copy_stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s.copied, 0));
-  } else {
-    HIPCHK(ctx, hipMemcpyAsync(s.d_raw, s.h_msgs, bytes, hipMemcpyHostToDevice, ctx->stream));
-  }
-  auto fail = [&](int lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; };
-  int lr = rgb_launch_prepare(ctx->dev, s.d_raw, n, R, ctx->d_srv_cnt, ctx->d_srv_list, ctx->d_prep, s.d_key, s.d_msgs,
-                              s.d_dec, s.d_pos, s.h_nrpc + 3, ctx->stream);
-  if (lr) return fail(lr);
+  const int rc = enqueue_copy_in(ctx, s, s.d_raw, (size_t)n * sizeof(rgb_msg));
+  if (rc) return rc;
+  LAUNCHCHK(ctx, rgb_launch_prepare(ctx->dev, s.d_raw, n, R, ctx->d_srv_cnt, ctx->d_srv_list, ctx->d_prep, s.d_key, s.d_msgs,
+                                    s.d_dec, s.d_pos, s.h_nrpc + 3, ctx->stream));
   for (u32 r = 0; r < R; ++r) {
     const u32 base = rgb_raw_round_base(n, r), bound = n / (r + 1u);
     if (!bound) break;
-    lr = rgb_launch_tick_classes(ctx->dev, s.d_msgs + base, nullptr, ctx->d_prep + RGB_PREP_COUNTS + r * RGB_N_FAMILIES,
-                                 bound, s.d_dec + base, s.d_rpcs, base, base, ctx->stream);
-    if (lr) return fail(lr);
+    LAUNCHCHK(ctx, rgb_launch_tick_classes(ctx->dev, s.d_msgs + base, nullptr, ctx->d_prep + RGB_PREP_COUNTS + r * RGB_N_FAMILIES,
+                                           bound, s.d_dec + base, s.d_rpcs, base, base, ctx->stream));
   }
   return enqueue_results(ctx, s);
-}
-
-/* step 3 for a slot whose ticket is `ticket`: wait for the turn, enqueue (unless rc already holds an error), publish
- * -- as failed if need be: the ticket is honoured whatever happens */
-static int publish_in_turn(rgb_ctx *ctx, rgb_slot &s, uint64_t ticket, int rc) {
-  {
-    std::unique_lock<std::mutex> el(ctx->enqueue_mu);
-    ctx->enqueue_cv.wait(el, [&] { return ctx->enqueue_turn == ticket; });
-    if (rc == RGB_OK) {
-      try { rc = enqueue_raw(ctx, s); } catch (...) { rc = RGB_E_NOMEM; }
-    }
-    if (rc != RGB_OK) {
-      s.enqueue_error = rc; s.n = 0;
-      (void)hipEventRecord(s.done, ctx->stream);
-    }
-    s.state.store(2, std::memory_order_release);
-    ctx->in_flight.fetch_add(1, std::memory_order_release);
-    ctx->enqueue_turn += 1;
-  }
-  ctx->enqueue_cv.notify_all();
-  { std::lock_guard<std::mutex> wl(ctx->wait_mu); }
-  ctx->wait_cv.notify_one();
-  return rc;
-}
-
-/* the next ring slot and a ticket (step 2 of rgb_submit); with_scratch: the slot's raw buffers exist when it is taken */
-static int take_slot(rgb_ctx *ctx, bool with_scratch, rgb_slot **out, uint64_t *ticket) {
-  std::lock_guard<std::mutex> lk(ctx->submit_mu);
-  rgb_slot *sp = &ctx->ring_mem[ctx->head];
-  if (sp->state.load(std::memory_order_acquire) != 0) return RGB_E_FULL;
-  if (with_scratch) {
-    const int rc = raw_scratch(ctx, *sp);
-    if (rc) return rc;                                       /* (nothing was taken) */
-  }
-  int free_state = 0;
-  if (!sp->state.compare_exchange_strong(free_state, 1, std::memory_order_acquire)) return RGB_E_FULL;
-  ctx->head = (ctx->head + 1) % ctx->ring_size;
-  *ticket = ctx->next_ticket++;
-  rgb_slot &s = *sp;
-  s.n = 0; s.n_ranges = 0; s.has_seqx = false; s.used_train = false; s.enqueue_error = 0; s.has_undo = false;
-  s.n_rounds = 0; s.n_touched = 0; s.raw = false;
-  *out = sp;
-  return RGB_OK;
 }
 
 /* a batch that is refused before anything is enqueued, as a per-batch result (the trains fall-back: there the host
@@ -1268,7 +1263,7 @@ static int publish_refused(rgb_ctx *ctx, int code, uint64_t tick) {
   const int rc = take_slot(ctx, false, &sp, &ticket);
   if (rc) return rc;
   sp->tick = tick;
-  (void)publish_in_turn(ctx, *sp, ticket, code);
+  (void)publish_in_turn(ctx, *sp, ticket, code, [] { return RGB_OK; });      /* (nothing to enqueue) */
   return RGB_OK;
 }
 
@@ -1320,7 +1315,7 @@ int rgb_submit_commit(rgb_ctx *ctx, uint32_t slot, uint32_t n, uint64_t tick) {
   s.h_pos = reinterpret_cast<u32 *>(s.h_msgs + ctx->cfg.ring_capacity);
   s.d_pos = reinterpret_cast<u32 *>(s.d_msgs + ctx->cfg.ring_capacity);
   s.begun.store(0, std::memory_order_release);
-  return publish_in_turn(ctx, s, s.raw_ticket, RGB_OK);
+  return publish_in_turn(ctx, s, s.raw_ticket, RGB_OK, [&] { return enqueue_raw(ctx, s); });
 }
 
 int rgb_submit_raw(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint32_t max_rounds, uint64_t tick) {
@@ -1330,21 +1325,17 @@ int rgb_submit_raw(rgb_ctx *ctx, const rgb_msg *msgs, uint32_t n, uint32_t max_r
   if (!ctx->registered) return RGB_E_STATE;
   if (n > rgb_submit_raw_capacity(ctx, R)) return RGB_E_INVAL;
   if (ctx->cfg.flags & RGB_CFG_SUBMIT_TRAINS) {
-    /* today's host passes; what they refuse because of the input becomes the batch's result, as on the device */
-    thread_local std::vector<unsigned char> seen;
-    if (seen.size() < ctx->dev.n_servers) seen.assign(ctx->dev.n_servers, 0);
-    bool too_many = false;
-    for (u32 i = 0; i < n; ++i)
-      if (msgs[i].kind != RGB_MSG_NOP && msgs[i].server < ctx->dev.n_servers && ++seen[msgs[i].server] > R) too_many = true;
-    for (u32 i = 0; i < n; ++i)
-      if (msgs[i].server < ctx->dev.n_servers) seen[msgs[i].server] = 0;
-    bool seqx = false;
-    for (u32 i = 0; i < n && !seqx; ++i) seqx = msgs[i].kind == RGB_MSG_WRITTEN && (msgs[i].flags & RGB_MF_SEQX);
-    int rc = RGB_OK;
-    for (u32 i = 0; i < n && rc == RGB_OK; ++i) rc = validate_msg(ctx, msgs[i]);
-    if (rc != RGB_OK || seqx) return publish_refused(ctx, RGB_E_INVAL, tick);
-    if (too_many) return publish_refused(ctx, RGB_E_UNSUPPORTED, tick);
-    return rgb_submit_seq(ctx, msgs, n, tick, nullptr, 0);
+    /* rgb_submit's host passes; what step 1 refuses because of the input becomes the batch's result, as on the
+     * device: an invalid record or one with a range list (no list here: validate_seqx refuses it) before a server with
+     * more than R messages */
+    HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+    submit_scan sc;
+    int bad = submit_prepare(ctx, msgs, n, nullptr, 0, R, sc);
+    /* (the pass stops at a server's 65 536th message: an invalid record may stand behind it) */
+    for (u32 i = 0; sc.too_many && bad != RGB_E_INVAL && i < n; ++i)
+      if (validate_msg(ctx, msgs[i]) != RGB_OK || validate_seqx(msgs[i], nullptr, 0) != RGB_OK) bad = RGB_E_INVAL;
+    if (bad) return publish_refused(ctx, bad, tick);
+    return submit_prepared(ctx, msgs, n, tick, nullptr, 0, sc);
   }
   rgb_fill f;
   const int rc = rgb_submit_begin(ctx, R, &f);
@@ -1407,15 +1398,13 @@ int rgb_run_ticks_device(rgb_ctx *ctx, const void *d_msgs, uint32_t tick_stride,
       u64 total = 0;
       for (u32 k = 1; k < NKIND; ++k) { cc[rgb_class_of_kind(k)] += kind_counts[t * NKIND + k]; total += kind_counts[t * NKIND + k]; }
       if (total > tick_stride || kind_counts[t * NKIND + RGB_MSG_NOP]) return RGB_E_INVAL;
-      int rc = launch_tick_classes(ctx, ctx->dev, m + off, d + off, (rgb_rpc *)d_rpcs, cc, 0, (u32)off, st);
-      if (rc) return rc;
+      LAUNCHCHK(ctx, rgb_launch_tick_classes(ctx->dev, m + off, cc, nullptr, 0, d + off, (rgb_rpc *)d_rpcs, 0, (u32)off, st));
       continue;
     }
     u32 cnt = tick_counts ? tick_counts[t] : tick_stride;
     if (cnt > tick_stride) return RGB_E_INVAL;
-    int rc = rgb_launch_tick(ctx->dev, -1, m + off, cnt, dn ? dn + t : nullptr, d + off, (rgb_rpc *)d_rpcs, 0,
-                             (u32)off, st);
-    if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_tick(ctx->dev, -1, m + off, cnt, dn ? dn + t : nullptr, d + off, (rgb_rpc *)d_rpcs, 0,
+                                   (u32)off, st));
   }
   return RGB_OK;
 }
@@ -1443,10 +1432,9 @@ int rgb_synth_tick_stamped_device(rgb_ctx *ctx, uint64_t seed, uint64_t tick, vo
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_synth_sent, bytes));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_synth_sent, ctx->dev.seq, bytes, hipMemcpyDeviceToDevice, (hipStream_t)st));
   }
-  int rc = rgb_launch_synth(ctx->dev, seed, tick, (rgb_msg *)d_msgs, ctx->d_synth, (u32 *)d_kind_counts,
-                            (u32 *)d_n, (u32 *)d_bucket_counts, (unsigned char *)d_stamps,
-                            d_stamps ? ctx->d_synth_sent : nullptr, st);
-  if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_synth(ctx->dev, seed, tick, (rgb_msg *)d_msgs, ctx->d_synth, (u32 *)d_kind_counts,
+                                  (u32 *)d_n, (u32 *)d_bucket_counts, (unsigned char *)d_stamps,
+                                  d_stamps ? ctx->d_synth_sent : nullptr, st));
   return RGB_OK;
 }
 
@@ -1460,8 +1448,7 @@ int rgb_synth_snapshot_mark_device(rgb_ctx *ctx, void *d_snap_stamps, void *stre
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_synth_sent, bytes));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_synth_sent, ctx->dev.seq, bytes, hipMemcpyDeviceToDevice, st));
   }
-  int lr = rgb_launch_seq_bump(ctx->d_synth_sent, (unsigned char *)d_snap_stamps, (u32)bytes, (void *)st);
-  if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_seq_bump(ctx->d_synth_sent, (unsigned char *)d_snap_stamps, (u32)bytes, (void *)st));
   return RGB_OK;
 }
 
@@ -1511,10 +1498,7 @@ static int train_scratch(rgb_ctx *ctx) {
     /* which XCCs does the device have?  A train block serves the shard(s) of the XCC it runs on (placement by
      * construction); the ids must be 0 .. n-1 with n dividing the 8 shards */
     HIPCHK(ctx, hipMemsetAsync(ctx->d_train_ctl + 1, 0, 2 * sizeof(u32), ctx->stream));
-    {
-      int rc = rgb_launch_train_calibrate(ctx->d_train_ctl + 1, ctx->stream);
-      if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
-    }
+    LAUNCHCHK(ctx, rgb_launch_train_calibrate(ctx->d_train_ctl + 1, ctx->stream));
     u32 cal[2] = {0, 0};
     HIPCHK(ctx, hipMemcpyAsync(cal, ctx->d_train_ctl + 1, sizeof cal, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1630,10 +1614,9 @@ int rgb_train_plan_build_device(rgb_ctx *ctx, rgb_train_plan *plan, uint32_t fir
   if (!ctx->registered || ctx->xcc_state != 1) return RGB_E_STATE;
   if (!plan->on_device || (uint64_t)first_tick + n_ticks > plan->n_ticks) return RGB_E_INVAL;
   void *st = stream ? stream : (void *)ctx->stream;
-  int lr = rgb_launch_train_plan((const u32 *)d_bucket_counts, plan->d_ticks, plan->d_rows, plan->bpt / RGB_TRAIN_SHARDS,
-                                 first_tick, n_ticks, plan->snap_every, ctx->dev.n_servers / ctx->dev.n_members,
-                                 ctx->dev.n_members, ctx->d_train_ctl, st);
-  if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_train_plan((const u32 *)d_bucket_counts, plan->d_ticks, plan->d_rows, plan->bpt / RGB_TRAIN_SHARDS,
+                                       first_tick, n_ticks, plan->snap_every, ctx->dev.n_servers / ctx->dev.n_members,
+                                       ctx->dev.n_members, ctx->d_train_ctl, st));
   for (u32 t = first_tick; t < first_tick + n_ticks; ++t) plan->rows_fit[t] = 0xFFFFFFFFu;      /* rebuilt: not known any more */
   return RGB_OK;
 }
@@ -1702,9 +1685,8 @@ int rgb_train_stamp_device(rgb_ctx *ctx, const void *d_msgs, void *d_stamps, uin
                              hipMemcpyDeviceToDevice, st));
   for (u32 t = 0; t < n_ticks; ++t) {
     if (tick_counts[t] > tick_stride) return RGB_E_INVAL;
-    int rc = rgb_launch_train_seq(ctx->dev, m + (size_t)t * tick_stride, tick_counts[t], ctx->d_seq_cnt,
-                                  sp + (size_t)t * tick_stride, st);
-    if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_train_seq(ctx->dev, m + (size_t)t * tick_stride, tick_counts[t], ctx->d_seq_cnt,
+                                        sp + (size_t)t * tick_stride, st));
   }
   return RGB_OK;
 }
@@ -1724,8 +1706,7 @@ int rgb_snapshot_train_device(rgb_ctx *ctx, void *d_rows, void *stream) {
   int rc = rgb_snapshot_device(ctx, d_rows, stream);
   if (rc) return rc;
   void *st = stream ? stream : (void *)ctx->stream;
-  int lr = rgb_launch_seq_bump(ctx->dev.seq, nullptr, ctx->dev.seq_stride * RGB_TRAIN_SHARDS, st);
-  if (lr) { ctx->last_hip.store(lr, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_seq_bump(ctx->dev.seq, nullptr, ctx->dev.seq_stride * RGB_TRAIN_SHARDS, st));
   return RGB_OK;
 }
 
@@ -1765,16 +1746,15 @@ int rgb_train_run_snap_device(rgb_ctx *ctx, const rgb_train_plan *plan, uint32_t
       for (u32 k = t; k < t + n && known; ++k) { known = plan->rows_fit[k] != 0xFFFFFFFFu; if (known && plan->rows_fit[k] > mx) mx = plan->rows_fit[k]; }
       if (known && mx * RGB_TRAIN_SHARDS <= plan->bpt) grid_bpt = (mx ? mx : 1u) * RGB_TRAIN_SHARDS;
     }
-    int rc = rgb_launch_train(ctx->dev, (const rgb_msg *)d_msgs + off, (const unsigned char *)d_stamps + off,
-                              tick_stride, plan->d_ticks + t, plan->d_rows + (size_t)t * (plan->bpt / RGB_TRAIN_SHARDS), n,
-                              grid_bpt, (rgb_decision *)d_decisions + off,
-                              (rgb_rpc *)d_rpcs, rpc_ring, (u32)off, ctx->d_train_ctl, ctx->n_xcc,
-                              /* (a device-built plan runs in the dealt form too: its grid is the rows BOUND of a tick --
-                               * rgb_train_rows_bound -- the blocks behind a tick's real rows find an empty table entry and exit) */
-                              ctx->train_dealt.load(std::memory_order_relaxed) ? 0u : ctx->train_blocks, st,
-                              (const unsigned char *)d_snap_stamps, (rgb_leaderboard_row *)d_snap_rows,
-                              plan->bpt / RGB_TRAIN_SHARDS);
-    if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+    LAUNCHCHK(ctx, rgb_launch_train(ctx->dev, (const rgb_msg *)d_msgs + off, (const unsigned char *)d_stamps + off,
+                                    tick_stride, plan->d_ticks + t, plan->d_rows + (size_t)t * (plan->bpt / RGB_TRAIN_SHARDS), n,
+                                    grid_bpt, (rgb_decision *)d_decisions + off,
+                                    (rgb_rpc *)d_rpcs, rpc_ring, (u32)off, ctx->d_train_ctl, ctx->n_xcc,
+                                    /* (a device-built plan runs in the dealt form too: its grid is the rows BOUND of a tick --
+                                     * rgb_train_rows_bound -- the blocks behind a tick's real rows find an empty table entry and exit) */
+                                    ctx->train_dealt.load(std::memory_order_relaxed) ? 0u : ctx->train_blocks, st,
+                                    (const unsigned char *)d_snap_stamps, (rgb_leaderboard_row *)d_snap_rows,
+                                    plan->bpt / RGB_TRAIN_SHARDS));
   }
   return RGB_OK;
 }
@@ -1806,9 +1786,8 @@ int rgb_synth_apply_tick_device(rgb_ctx *ctx, const void *d_msgs, uint32_t max_m
   if (!ctx || !d_msgs || !d_decisions) return RGB_E_INVAL;
   if (!ctx->registered || !ctx->d_synth) return RGB_E_STATE;
   void *st = stream ? stream : (void *)ctx->stream;
-  int rc = rgb_launch_tick_classes(ctx->dev, (const rgb_msg *)d_msgs, nullptr, ctx->d_synth, max_msgs,
-                                   (rgb_decision *)d_decisions, (rgb_rpc *)d_rpcs, 0, 0, st);
-  if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_tick_classes(ctx->dev, (const rgb_msg *)d_msgs, nullptr, ctx->d_synth, max_msgs,
+                                         (rgb_decision *)d_decisions, (rgb_rpc *)d_rpcs, 0, 0, st));
   return RGB_OK;
 }
 
@@ -1816,8 +1795,7 @@ int rgb_snapshot_device(rgb_ctx *ctx, void *d_rows, void *stream) {
   if (!ctx || !d_rows) return RGB_E_INVAL;
   if (!ctx->registered) return RGB_E_STATE;
   void *st = stream ? stream : (void *)ctx->stream;
-  int rc = rgb_launch_leaderboard(ctx->dev, (rgb_leaderboard_row *)d_rows, st);
-  if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_leaderboard(ctx->dev, (rgb_leaderboard_row *)d_rows, st));
   return RGB_OK;
 }
 
@@ -1968,8 +1946,7 @@ int rgb_state_checksum(rgb_ctx *ctx, uint32_t first, uint32_t n, uint64_t *out) 
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
   rgb_stream_turn turn(ctx);                               /* d_sums is shared */
   if (turn.rc) return turn.rc;
-  int rc = rgb_launch_checksum(ctx->dev, first, n, ctx->d_sums, ctx->stream);
-  if (rc) { ctx->last_hip.store(rc, std::memory_order_relaxed); return RGB_E_HIP; }
+  LAUNCHCHK(ctx, rgb_launch_checksum(ctx->dev, first, n, ctx->d_sums, ctx->stream));
   std::vector<u64> sums(n);
   HIPCHK(ctx, hipMemcpyAsync(sums.data(), ctx->d_sums, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost,
                              ctx->stream));

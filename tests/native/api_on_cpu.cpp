@@ -8,3 +8,7 @@
 #define RGB_HOST_EMULATION 1
 #include <hip/hip_runtime.h>
 #include "../../ra_amd/csrc/rgb_api.hip"
+
+/* the k-th hipMemcpyAsync of the emulation from now on fails once with EMU_INJECTED_HIP_ERROR (k <= 0: disarmed);
+ * returns that code (tests/test_submit_raw.py: a failed enqueue) */
+extern "C" int emu_fail_hip_copy(int k) { emu_fail_copy_countdown = k > 0 ? k : 0; return EMU_INJECTED_HIP_ERROR; }

@@ -66,7 +66,15 @@ enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMe
 static inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) { memset(p, v, n); return hipSuccess; }
 static inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : 2; }
 static inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
+/* fault hook (emu_fail_hip_copy, api_on_cpu.cpp): armed with k, the k-th hipMemcpyAsync from then on copies nothing and
+ * fails, once -- the only way the library's HIP error paths run at all (they must never be provoked on a device) */
+#define EMU_INJECTED_HIP_ERROR 719
+inline int emu_fail_copy_countdown = 0;
+static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) {
+  if (emu_fail_copy_countdown > 0 && --emu_fail_copy_countdown == 0) return EMU_INJECTED_HIP_ERROR;
+  memcpy(d, s, n);
+  return hipSuccess;
+}
 static inline hipError_t hipMemcpy2D(void *d, size_t dpitch, const void *s, size_t spitch, size_t width, size_t height, hipMemcpyKind) {
   for (size_t r = 0; r < height; ++r) memcpy((char *)d + r * dpitch, (const char *)s + r * spitch, width);
   return hipSuccess;

@@ -175,15 +175,19 @@ def check_refusals(engine, O, flags=0, groups=24, n_members=3, seed=31):
             for where in ("first", "middle", "last"):
                 cases.append((name, where, rec, code))
         cases.append(("too_many_rounds", "last", None, abi.E_UNSUPPORTED))
+        # an invalid record BEHIND a server that is already over max_rounds: the input error wins
+        cases.append(("aer_run0", "behind too_many_rounds", {n: r for n, r, _ in bad_records(S)}["aer_run0"], abi.E_INVAL))
         ways = ("collect", "peek", "view")
         for k, (name, where, rec, code) in enumerate(cases):
             good = multi_round_batch(rng, cpu.get_state(), n_members, 2)
-            if rec is None:
+            if rec is None or where == "behind too_many_rounds":
                 # max_rounds + 1 messages for one server (every one of them valid)
                 srv = int(good["server"][good["kind"] != abi.MSG_NOP][0])
                 extra = np.zeros(R + 1, dtype=abi.MSG_DTYPE)
                 extra["server"], extra["kind"] = srv, abi.MSG_PIPELINE_RPCS
                 batch = np.concatenate([good[good["server"] != srv], extra])
+                if rec is not None:
+                    batch = np.concatenate([batch, np.array([rec], dtype=abi.MSG_DTYPE)])
             else:
                 at = {"first": 0, "middle": len(good) // 2, "last": len(good)}[where]
                 batch = np.concatenate([good[:at], np.array([rec], dtype=abi.MSG_DTYPE), good[at:]])
@@ -294,6 +298,86 @@ def test_gpu_refused_batches_are_per_batch_results(gpu_engine, oracle_lib):
 @pytest.mark.gpu
 def test_gpu_synchronous_errors(gpu_engine):
     check_synchronous_errors(gpu_engine)
+
+
+# ------------------------------------------------------------------------------------------ 2b. a failed enqueue
+
+def send(gpu, form, msgs, tick, max_rounds):
+    if form == "submit":
+        gpu.submit(msgs, tick=tick)
+    elif form == "submit_raw":
+        gpu.submit_raw(msgs, tick=tick, max_rounds=max_rounds)
+    else:
+        fill_and_commit(gpu, msgs, tick, max_rounds)
+
+
+def check_failed_enqueue(engine, O, form, flags, groups=24, n_members=3, seed=43):
+    """The batch's message copy -- its first stream operation -- fails (the emulation's emu_fail_hip_copy; a device is
+    never made to fail): the submitting call returns RGB_E_HIP with the injected code in rgb_last_hip_error, the batch
+    is published as failed (collect reports RGB_E_HIP once, then the ring is empty), nothing was applied, and the
+    ticket was honoured: the next batches on the same servers, through the same form and through another one, take
+    their turn and equal the checker's."""
+    import ctypes
+    L = engine.lib()
+    L.emu_fail_hip_copy.restype, L.emu_fail_hip_copy.argtypes = ctypes.c_int, [ctypes.c_int]
+    rng = np.random.default_rng(seed)
+    st = fuzz.random_states(rng, groups, n_members, max_runs=6)
+    cpu = O.Oracle(groups, n_members, max_runs=16)
+    cpu.set_state(0, st)
+    R = 3
+    other = "submit_raw" if form == "submit" else "submit"
+
+    def good_batch(gpu, via, tick, tag):
+        good = multi_round_batch(rng, cpu.get_state(), n_members, 2)
+        do, ro = cpu.step(good)
+        send(gpu, via, good, tick, R)
+        dg, rg, t = gpu.collect()
+        assert t == tick and dg.tobytes() == do.tobytes(), tag + ": decisions"
+        assert fuzz.sort_rpcs(rg.copy()).tobytes() == fuzz.sort_rpcs(ro).tobytes(), tag + ": rpcs"
+        assert_state_equal(tag, gpu.get_state(), cpu.get_state())
+
+    with engine.RaGpuBatch(groups, n_members, ring_capacity=1024, ring_slots=2, max_runs=16, flags=flags) as gpu:
+        gpu.set_state(0, st)
+        good_batch(gpu, form, 1, "in front of the failed batch")
+        lost = multi_round_batch(rng, cpu.get_state(), n_members, 2)       # the checker never sees it
+        before_sum, before = gpu.state_checksum(), gpu.get_state()
+        injected = L.emu_fail_hip_copy(1)                                  # the next copy: the batch's messages
+        try:
+            with pytest.raises(engine.RgbError) as e:
+                send(gpu, form, lost, 2, R)
+        finally:
+            L.emu_fail_hip_copy(0)
+        assert injected != 0 and (e.value.code, e.value.hip) == (abi.E_HIP, injected), (e.value.code, e.value.hip)
+        assert gpu._L.rgb_last_hip_error(gpu._h) == injected
+        expect_error(engine, gpu.collect, abi.E_HIP)                       # .. exactly once: the ring moved on
+        expect_error(engine, gpu.collect, abi.E_EMPTY)
+        assert gpu.in_flight == 0
+        assert gpu.state_checksum() == before_sum, "the failed batch changed the state checksum"
+        assert_state_equal("the failed batch applied something", gpu.get_state(), before)
+        good_batch(gpu, form, 3, f"{form} behind the failed batch")
+        good_batch(gpu, other, 4, f"{other} behind the failed batch")
+    cpu.close()
+
+
+@pytest.mark.parametrize("flags", [0, abi.CFG_SUBMIT_TRAINS])
+@pytest.mark.parametrize("form", ["submit", "submit_raw", "begin_commit"])
+def test_failed_enqueue_is_published_and_honours_its_ticket(emulated_engine, oracle_lib, form, flags):
+    """In a worker thread joined with a timeout: a ticket that is not honoured blocks every later submit for ever, and
+    that must fail this test, not hang the run."""
+    errs = []
+
+    def run():
+        try:
+            check_failed_enqueue(emulated_engine, oracle_lib, form, flags)
+        except BaseException as e:                                   # noqa: BLE001
+            errs.append(e)
+
+    t = threading.Thread(target=run, daemon=True)
+    t.start()
+    t.join(60)
+    assert not t.is_alive(), "a submit behind the failed batch never got its turn"
+    if errs:
+        raise errs[0]
 
 
 # ------------------------------------------------------------------------------------------ 3. ordering
@@ -412,6 +496,22 @@ def check_trains_fallback(engine, O, G=1200, N=5):
 
 def test_trains_fallback_on_the_emulation(emulated_engine, oracle_lib):
     check_trains_fallback(emulated_engine, oracle_lib)
+
+
+def test_trains_fallback_sees_an_invalid_record_behind_65536_messages_of_one_server(emulated_engine):
+    """rgb_submit's pass over the batch stops at a server's 65 536th message; the raw call still reports the invalid
+    record behind it (RGB_E_INVAL before RGB_E_UNSUPPORTED), and RGB_E_UNSUPPORTED when there is none."""
+    engine = emulated_engine
+    with engine.RaGpuBatch(8, 3, ring_capacity=65540, ring_slots=1, flags=abi.CFG_SUBMIT_TRAINS) as gpu:
+        batch = np.zeros(65537, dtype=abi.MSG_DTYPE)
+        batch["server"], batch["kind"] = 5, abi.MSG_PIPELINE_RPCS
+        before = gpu.state_checksum()
+        for last, code in ((batch[0], abi.E_UNSUPPORTED), (dict((n, r) for n, r, _ in bad_records(24))["aer_run0"], abi.E_INVAL)):
+            batch[-1] = last
+            gpu.submit_raw(batch, max_rounds=1)
+            expect_error(engine, gpu.collect, code)
+            expect_error(engine, gpu.collect, abi.E_EMPTY)
+            assert gpu.state_checksum() == before
 
 
 @pytest.mark.gpu
