@@ -286,6 +286,9 @@ typedef struct rgb_decision {
  *   confirmed   kind AER or WRITTEN with RGB_F_REPLY | RGB_F_REPLY_SUCCESS: reply_next_index = A + 1, reply_term = B,
  *               reply_last_index = A - aux[0:8], reply_last_term = B - aux[8:12],
  *               commit_index = A + aux[12:22] - 512, last_applied = A + 1 - aux[22:32]
+ * Beside the flags that name its form a compacted decision carries only flags that come with no words of their own:
+ * RGB_F_LEADER_MSG, RGB_F_APPLIED, RGB_F_AUX_EVAL, RGB_F_PIPELINE.  Every difference above is taken in the integers: a
+ * negative one (reply_last_index above A, last_applied above A + 1, ..) does not fit, nor does reply_next_index = 0.
  * A decision whose values do not fit (or that is of any other shape) is written in full, without the flag: the
  * encoding loses nothing.  The kernels compact at the store; rgb_decision_expand is the only decoder a consumer needs. */
 static inline void rgb_decision_expand(rgb_decision *d) {

@@ -78,8 +78,15 @@ struct ora_ctx {
   oserver *sv;
 };
 
+/* the array holds what lies between two indexes of ONE range: a distance no log has is an error of the caller's,
+ * refused before the size arithmetic can wrap (realloc of 0 bytes frees the block) */
+#define OLOG_MAX_SPAN ((uint64_t)1 << 32)
+
 static int log_reserve(olog *l, uint64_t idx) {
   /* make terms[idx - base] addressable */
+  if (l->terms != NULL && !l->has_range) l->base = idx;    /* no range: nothing stored counts, however far away the
+                                                              next one starts (a snapshot written far ahead of the log) */
+  if (l->terms != NULL && (idx < l->base ? l->base - idx : idx - l->base) >= OLOG_MAX_SPAN) return -1;
   if (l->terms == NULL) {
     l->cap = 64;
     l->terms = (uint64_t *)malloc(l->cap * sizeof(uint64_t));
@@ -238,7 +245,14 @@ static int log_write(olog *l, const rgb_msg *m, uint32_t k0) {
     lwt = log_fetch_term(l, lwi);
     if (lwt == UNDEF) return RGB_INV_LAST_WRITTEN_TERM;    /* true = Term2 =/= undefined */
   }
-  if (log_reserve(l, fst) || log_reserve(l, lst)) return RGB_INV_WRITE_INTEGRITY;
+  if (log_reserve(l, fst)) return RGB_INV_WRITE_INTEGRITY;
+  {
+    const int had = l->has_range;                           /* (an empty log restarts its array at fst, once) */
+    l->has_range = 1;
+    const int rc = log_reserve(l, lst);
+    l->has_range = had;
+    if (rc) return RGB_INV_WRITE_INTEGRITY;
+  }
   for (uint32_t k = k0; k < m->n_entries; k++)
     l->terms[msg_first_index(m) + k - l->base] = msg_entry_term(m, k);
   if (!l->has_range) { l->has_range = 1; l->first = fst; }

@@ -129,8 +129,10 @@ def _term_at(row, idx):
 
 
 def random_msgs(rng: np.random.Generator, st: np.ndarray, n_members: int, frac: float = 0.9,
-                transfers: float = 0.0) -> np.ndarray:
+                transfers: float = 0.0, wide: bool = False) -> np.ndarray:
     """At most one message per server (a tick), for a random `frac` of the servers, shuffled.
+    wide (opt-in; False draws nothing more): the values that do not follow from the state are drawn to match a
+    widen()ed one -- see _widen_msgs.
     transfers (opt-in; 0 draws nothing more): that share of the messages becomes the call {transfer_leadership, Target}
     with Target drawn from self, the peers level with ra_log:next_index/1, the other members, a slot beyond the group
     and RGB_NONE; a server that awaits RGB_COND_TRANSFER_LEADERSHIP gets a raised share of the two messages that end
@@ -263,7 +265,86 @@ def random_msgs(rng: np.random.Generator, st: np.ndarray, n_members: int, frac: 
         _ = self_
     if transfers > 0.0:
         _mix_in_transfers(rng, m, st, n_members, transfers)
+    if wide:
+        _widen_msgs(rng, m, st)
     return m
+
+
+def _near_token(rng, token: int) -> int:
+    """The token itself, or one that differs from it in one bit of either word, or a fresh 64-bit one."""
+    u = rng.random()
+    if u < 0.5:
+        return token
+    if u < 0.7:
+        return token ^ (1 << int(rng.integers(32, 64)))           # same low word
+    if u < 0.85:
+        return token ^ (1 << int(rng.integers(0, 32)))            # same high word
+    return int(rng.integers(0, 2**64, dtype=np.uint64))
+
+
+def _widen_msgs(rng, m, st):
+    """Tokens over 64 bits (the server's own, or one bit away in either word), candidate machine versions around the
+    server's two versions over the whole u32 range, query indexes around the server's own."""
+    for q in range(len(m)):
+        row = st[int(m["server"][q])]
+        kind = int(m["kind"][q])
+        if kind == abi.MSG_ELECTION_TIMEOUT:
+            m["c"][q] = int(rng.integers(0, 2**64, dtype=np.uint64))
+        elif kind == abi.MSG_PRE_VOTE_RPC:
+            m["c"][q] = int(rng.integers(0, 2**64, dtype=np.uint64))
+            v = int(row[str(rng.choice(["machine_version", "effective_machine_version"]))]) + int(rng.integers(-1, 2))
+            m["n_entries"][q] = min(max(v, 0), 0xFFFFFFFF)
+        elif kind == abi.MSG_PRE_VOTE_RESULT:
+            m["c"][q] = _near_token(rng, int(row["pre_vote_token"]))
+        elif kind in (abi.MSG_HEARTBEAT_RPC, abi.MSG_HEARTBEAT_REPLY):
+            m["a"][q] = max(0, int(row["query_index"]) + int(rng.integers(-3, 4)))
+
+
+WIDE_LIMIT = abi.UNDEF_INT - 2**16      # widen() keeps every value below this: RGB_UNDEF's neighbourhood is no index
+
+
+def widen(st: np.ndarray, n_members: int, index_offset: int, term_offset: int, rng=None) -> np.ndarray:
+    """A copy of `st` with index_offset added to every index and term_offset to every term: the scalar cursors, the
+    live members' peer columns, the runs in use, the snapshot where there is one, the stored reply of a server in
+    await_condition and the live ranges of pending_old.  The result is the same log seen from further along -- every
+    difference the clauses form is unchanged, every absolute value is wide.
+    rng (opt-in): the values that are not indexes or terms are drawn wide as well -- a 64-bit pre_vote_token,
+    machine versions over the whole u32 range (0xFFFFFFFF included) with the effective version below, at and above
+    the real one, query indexes near the index offset."""
+    w = st.copy()
+    io, to = np.uint64(index_offset), np.uint64(term_offset)
+    for f in ("commit_index", "last_applied", "last_index", "last_written_index", "first_index", "pending_first"):
+        w[f] += io
+    for f in ("current_term", "last_term", "last_written_term"):
+        w[f] += to
+    for f in ("match_index", "next_index", "commit_index_sent"):
+        w[f][:, :n_members] += io
+    used = np.arange(abi.MAX_RUNS)[None, :] < w["n_runs"][:, None]
+    w["run_start"][used] += io
+    w["run_term"][used] += to
+    snap = w["snapshot_index"] != abi.UNDEF
+    w["snapshot_index"][snap] += io
+    w["snapshot_term"][snap] += to
+    waiting = w["role"] == abi.ROLE_AWAIT_CONDITION
+    w["cond_reply"][waiting, 0] += to
+    w["cond_reply"][waiting, 1] += io
+    w["cond_reply"][waiting, 2] += io
+    w["cond_reply"][waiting, 3] += to
+    live = np.arange(2)[None, :] < w["n_pending_old"][:, None]
+    w["pending_old"][live] += io
+    if rng is not None:
+        S = len(w)
+        w["pre_vote_token"] = rng.integers(0, 2**64, size=S, dtype=np.uint64)
+        mv = rng.choice(np.array([0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFE, 0xFFFFFFFF], dtype=np.int64), size=S)
+        rnd = rng.random(S) < 0.4
+        mv[rnd] = rng.integers(0, 2**32, size=int(rnd.sum()), dtype=np.int64)
+        w["machine_version"] = mv
+        w["effective_machine_version"] = np.clip(mv + rng.integers(-1, 2, size=S), 0, 0xFFFFFFFF)
+        w["query_index"] = io + rng.integers(0, 6, size=S).astype(np.uint64)
+        w["peer_query_index"][:, :n_members] = io + rng.integers(0, 6, size=(S, n_members)).astype(np.uint64)
+    for f in ("commit_index", "last_index", "current_term", "last_term"):
+        assert int(w[f].max()) < WIDE_LIMIT, f
+    return w
 
 
 def _mix_in_transfers(rng, m, st, n_members, share):

@@ -11,9 +11,12 @@ import fuzz
 from ra_amd import abi
 
 
-def check_fused(engine, oracle_lib, n_members, groups, seed, ticks=4):
+def check_fused(engine, oracle_lib, n_members, groups, seed, ticks=4, offsets=None):
+    """offsets (opt-in): (index offset, term offset) of fuzz.widen -- the same run on full-width values."""
     rng = np.random.default_rng(seed)
     st = fuzz.random_states(rng, groups, n_members, max_runs=6)
+    if offsets is not None:
+        st = fuzz.widen(st, n_members, *offsets)
     S = groups * n_members
     cpu = oracle_lib.Oracle(groups, n_members)
     cpu.set_state(0, st)

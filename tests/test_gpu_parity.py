@@ -680,6 +680,12 @@ def test_quorum_term_gate_on_any_run_table(engine_mod, oracle_lib, groups, seed)
     trusted the flag blindly fails here."""
     rng = np.random.default_rng(seed)
     N = 5
+    st = quorum_gate_states(rng, groups, N)
+    check_quorum_term_gate(engine_mod, oracle_lib, st, groups, N, rng)
+
+
+def quorum_gate_states(rng, groups, N):
+    """Leaders in slot 0 over run tables Raft can produce and ones it cannot (see the test above)."""
     st = abi.empty_server_states(groups, N)
     for s in range(groups * N):
         n_runs = int(rng.integers(1, 7))
@@ -715,6 +721,12 @@ def test_quorum_term_gate_on_any_run_table(engine_mod, oracle_lib, groups, seed)
             st["match_index"][s, j] = mi
             st["next_index"][s, j] = mi + 1 + int(rng.integers(0, 3))
             st["commit_index_sent"][s, j] = st["commit_index"][s]
+    return st
+
+
+def check_quorum_term_gate(engine_mod, oracle_lib, st, groups, N, rng):
+    """Six ticks of success replies to the leaders of `st`: decisions, rpc records and states equal the checker's, and
+    the gate opened often enough to matter."""
     cpu = oracle_lib.Oracle(groups, N)
     cpu.set_state(0, st)
     moved = 0
@@ -726,7 +738,7 @@ def test_quorum_term_gate_on_any_run_table(engine_mod, oracle_lib, groups, seed)
             for g in range(groups):
                 s = g * N
                 li, first = int(cur["last_index"][s]), int(cur["first_index"][s])
-                last = int(rng.integers(first, li + 1))
+                last = first + int(rng.integers(0, li + 1 - first))      # (li may lie above 2^63: draw the distance)
                 msgs.append(_reply_ok(s, int(rng.integers(1, N)), int(cur["current_term"][s]), last + 1, last))
             msgs = np.array(msgs, dtype=abi.MSG_DTYPE)
             do, ro = cpu.step(msgs)
