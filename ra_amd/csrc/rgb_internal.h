@@ -92,6 +92,14 @@ typedef uint32_t u32;
 #define PK_QPEER_SH     57  /* 1: some peer query_index > 0 (reset_query_index has work) */
 #define PK_BACKOFF_SH   58  /* 1: some peer is in {snapshot_backoff,_}: qry row word QRY_BACKOFF holds the mask */
 #define PK_PENDX_SH     59  /* 1: `pending` has ranges below its newest one: qry row words QRY_PEND_LO.. hold them */
+#define PK_CANON_SH     60  /* 1: the run table is CANONICAL -- with n_runs >= 1: run terms strictly increasing, run starts strictly
+                               increasing, start of run 0 <= first_index.  Then every index of the range lies in a run, and an
+                               index of the range below the last run's start has a DEFINED term BELOW the last run's: the
+                               quorum term gate (quorum_term_gate) answers from the row alone.  Set by rgb_pack_kernel for a
+                               table it has verified and by the first push onto an empty table; cleared by a push that breaks
+                               the order (push_segment); kept by truncation, compaction and overflow, which drop runs from
+                               either end or raise run 0's start to the new first_index.  A cleared bit only costs the walk.
+                               Derived state: rgb_unpack_kernel, rgb_checksum_kernel and the load generator never see it */
 /* the condition field (COND 2 bits, CONDTO 1 bit) <-> rgb_server_state.cond_reason */
 static inline __host__ __device__ unsigned pk_cond_reason(u64 pk) {
   const unsigned c = (unsigned)((pk >> PK_COND_SH) & 3ull), to = (unsigned)((pk >> PK_CONDTO_SH) & 1ull);

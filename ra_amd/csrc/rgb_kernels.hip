@@ -457,6 +457,28 @@ __device__ __forceinline__ u64 srv_fetch_term(const Lane &L, u64 idx) {
   return t;
 }
 
+/* The Raft 5.4.2 gate of a quorum evaluation (evaluate_quorum/2, src/ra_server.erl:3633-3646): is the term of the agreed
+ * index p the current term?  = srv_fetch_term(p) == current_term, written over the row's words so that the general path
+ * (evaluate_quorum) and the success-reply fast path (fast_aer_reply) share it.
+ * The walk that is foregone: p inside the range and below the last run's start, on a row whose table is canonical
+ * (PK_CANON_SH) and whose last-run term is not above the current term.  p then lies in one of the runs 0 .. n_runs-2
+ * (run 0 starts at or below first_index <= p), whose terms are strictly below lrt <= current_term: the term is defined --
+ * the snapshot clause does not apply -- and is not the current one, whatever the table holds.  walk() is only called for
+ * what is left: the term of an in-range p below the last run's start (the mirrored run n_runs-2, then the table), UNDEF
+ * if no run holds it. */
+template <class Walk>
+__device__ __forceinline__ bool quorum_term_gate(u64 pk, unsigned n_runs, u64 ct, u64 first, u64 li, u64 lrs, u64 lrt,
+                                                 u64 si, u64 st, u64 p, Walk walk) {
+  u64 t = UNDEF;
+  if (first <= li && p >= first && p <= li) {
+    if (p >= lrs) t = lrt;
+    else if (pk_get(pk, PK_CANON_SH, 1) && n_runs >= 1u && lrt <= ct) return false;
+    else t = walk();
+  }
+  if (t == UNDEF && si != UNDEF && si == p) t = st;
+  return t != UNDEF && t == ct;
+}
+
 /* index of the run holding idx (largest k with start_k <= idx), -1 if none.  Only called
  * before any edit of this message is pending. */
 template <class Lane>
@@ -744,6 +766,10 @@ __device__ __forceinline__ void evaluate_commit_index_follower(Lane &L) {
 template <class Lane>
 __device__ __forceinline__ void push_segment(Lane &L, u64 s, u64 t) {
   if (L.n_runs > 0 && L.lrt == t) return;            /* extends the last run */
+  /* PK_CANON_SH: the first run of an empty table makes it canonical iff it starts at or below first_index; a later
+   * run keeps it only above the last run in term AND start (an append_entries_rpc may carry entries of any term) */
+  if (L.n_runs == 0) L.pk = pk_set(L.pk, PK_CANON_SH, 1, s <= L.first ? 1ull : 0ull);
+  else if (t < L.lrt || s <= L.lrs) L.pk &= ~(1ull << PK_CANON_SH);
   L.prs = L.lrs; L.prt = L.lrt;                      /* the old last run is now run n-2 */
   L.push_cnt += 1;
   L.n_runs += 1;
@@ -1187,8 +1213,9 @@ __device__ __forceinline__ void evaluate_quorum(Lane &L) {
   }
   const u64 ci0 = L.ci;
   u64 p = agreed_commit<N + 1>(v, use, n);
-  u64 t = srv_fetch_term(L, p);
-  if (t != UNDEF && t == L.ct) L.ci = p;           /* Raft 5.4.2; NO max() */
+  if (quorum_term_gate(L.pk, L.n_runs, L.ct, L.first, L.li, L.lrs, L.lrt, L.si, L.st, p,
+                       [&]() __attribute__((always_inline)) { return fetch_term(L, p); }))
+    L.ci = p;                                      /* Raft 5.4.2; NO max() */
   if (L.ci > ci0) L.flags |= RGB_F_AUX_EVAL;
   if (apply_to(L, L.ci)) L.flags |= RGB_F_APPLIED;
 }
@@ -2603,10 +2630,12 @@ __device__ __forceinline__ bool fast_aer_reply(const rgb_dev &dev, const ulonglo
     v[i] = wm[i]; use[i] = u; n += u ? 1 : 0;
   }
   const u64 p = agreed_commit<N + 1>(v, use, n);
-  u64 t = UNDEF;
-  if (first <= li && p >= first && p <= li) {
-    if (p >= lrs) t = lrt;
-    else if (n_runs >= 2 && p >= prs) t = prt;
+  /* the gate from the row (quorum_term_gate): a canonical row answers an agreed index below its last run without the
+   * table -- the success-reply rows of a train fetch no table line (rrow is null there) */
+  bool found = true;
+  const bool current = quorum_term_gate(pk, n_runs, ct, first, li, lrs, lrt, si, st, p, [&]() __attribute__((always_inline)) {
+    u64 t = UNDEF;
+    if (n_runs >= 2 && p >= prs) t = prt;
     else {
       /* older than the mirrored runs: the newest in-memory run (n_runs-3 .. 0) that starts at or below p holds it
        * (ra_log:fetch_term/2 inside the range, src/ra_log.erl:1186-1200).  Train launches: runs 0..7 are in the table
@@ -2614,7 +2643,7 @@ __device__ __forceinline__ bool fast_aer_reply(const rgb_dev &dev, const ulonglo
        * of more than ten runs: 3 % of the lanes of the closed loop, but two wavefronts in three had one and ran the
        * whole general path for it (round 5) -- and every run of a per-tick launch are read from the table itself,
        * newest first */
-      bool found = false;
+      found = false;
       const ulonglong2 *rt = reinterpret_cast<const ulonglong2 *>(dev.runs + (size_t)server * dev.max_runs * 2u);
       const int lds_runs = rrow != nullptr ? RGB_RUNS_LDS : 0;
 #pragma unroll 1
@@ -2631,14 +2660,14 @@ __device__ __forceinline__ bool fast_aer_reply(const rgb_dev &dev, const ulonglo
           }
         }
       }
-      if (!found) FP_DECLINE(1, 8);
     }
-  }
+    return t;
+  });
+  if (!found) FP_DECLINE(1, 8);              /* below the oldest run: the general path (nothing has been stored yet) */
   FP_TAKEN(1);
-  if (t == UNDEF && si != UNDEF && si == p) t = st;
   u64 ci = ci0, nla = la;
   u32 flags = RGB_F_PIPELINE;
-  if (t != UNDEF && t == ct) ci = p;                                 /* Raft 5.4.2; NO max() */
+  if (current) ci = p;                                               /* Raft 5.4.2; NO max() */
   if (ci > ci0) flags |= RGB_F_AUX_EVAL;
   if (ci > la) { const u64 to = li < ci ? li : ci; if (to >= la + 1) { nla = to; flags |= RGB_F_APPLIED; } }
   /* the two words are one 16-byte piece of the row: stored whole when either moved (the other keeps its value; a 16-byte
@@ -2838,7 +2867,7 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
                                                const unsigned char *__restrict__ stamps,
                                                u32 *__restrict__ ticket_ctr = nullptr, u32 *next_ticket = nullptr,
                                                u32 shard = 0, u32 lane_in = 0, const u32 *place_word = nullptr,
-                                               u32 place_bit = 0) {
+                                               u32 place_bit = 0, const u32 sub = 0 /* the row's sub-bucket (plan class & 1) */) {
   const u32 lane = TR ? lane_in : (u32)threadIdx.x;     /* the persistent loop hands in an opaque copy */
 #ifdef RGB_PROFILE
   u64 t0 = 0, t1 = 0, t2 = 0, t2b = 0, tl[4] = {0, 0, 0, 0};
@@ -2850,7 +2879,13 @@ __device__ __forceinline__ bool rgb_tick_slice(const rgb_dev &dev, ulonglong2 *i
    * peers rows come into LDS cooperatively (rgb_train_class_slice) */
   constexpr bool PEERS_WIDE = TR && rgb_train_class_slice(1, (unsigned)N) == 32u && !PEERS_LDS;
   /* a table row of max_runs >= 8 runs holds the whole 128-byte line that is fetched (wave-uniform) */
-  const bool RUNS_LDS = TR && (PEERS_LDS || PEERS_WIDE) && dev.max_runs >= (u32)RGB_RUNS_LDS;
+  /* NOT for the success-reply rows (class 1, sub-bucket 1 = the reply's success flag): all such a message asks of the
+   * table is the quorum term gate, which a canonical row answers by itself (quorum_term_gate) -- no table line is
+   * fetched, rrow is null, and a lane whose row is not canonical, or that is no success reply after all (the sub-bucket
+   * only orders a tick), walks from memory as tables of more than ten runs always did.  Fused pipelining
+   * (RGB_CFG_FUSE_PIPELINE) shapes rpcs behind the reply and keeps the line. */
+  const bool RUNS_LDS = TR && (PEERS_LDS || PEERS_WIDE) && dev.max_runs >= (u32)RGB_RUNS_LDS &&
+                        !(cls == 1 && sub != 0u && dev.fuse_pipeline == 0u);
   /* groups of six and more members (no peers rows in LDS: the area is free): an append_entries_rpc wavefront whose
    * messages point below the current term's entries (prev_log_term != term in any lane: log-matching repair, the
    * configs[4] workload) will walk its servers' run tables -- their first line comes with the hot rows (decided
@@ -3437,7 +3472,7 @@ __global__ __launch_bounds__(RGB_TICK_BLOCK, RGB_TRAIN_MIN_WAVES(N)) void rgb_tr
   (void)rgb_tick_slice<N, true>(args.dev, io, cls, off + lbase, cnt, SL, args.msgs + toff, args.dec + toff, rp, 0,
                                 args.index_base + (u32)toff, args.ctl, args.stamps + toff, nullptr, &unused, x,
                                 threadIdx.x, args.ctl + RGB_TRAIN_CTL_MARK + 32u * (k & (RGB_TRAIN_MARK_WORDS - 1u)),
-                                1u << ((rgb_xcc_id() - x) & (RGB_TRAIN_SHARDS - 1u)));
+                                1u << ((rgb_xcc_id() - x) & (RGB_TRAIN_SHARDS - 1u)), pc & 1u);
 }
 
 /* BEHIND every train launch (rgb_launch_train): the rotation marks the dealt launch left on these control words must
@@ -3531,7 +3566,7 @@ __global__ __launch_bounds__(RGB_TICK_BLOCK, RGB_TRAIN_PERSIST_MIN_WAVES(N)) voi
     lds_barrier();                                        /* the previous slice is done with the staging area */
     raw = 0;
     if (!rgb_tick_slice<N, true>(dev, io, cls, off + lbase, cnt, SL, A->msgs + toff, A->dec + toff, rp, 0,
-                                 A->index_base + (u32)toff, A->ctl, A->stamps + toff, tk, &raw, x, lane))
+                                 A->index_base + (u32)toff, A->ctl, A->stamps + toff, tk, &raw, x, lane, nullptr, 0, pc & 1u))
       break;
   }
 }
@@ -3910,6 +3945,7 @@ __global__ void rgb_pack_kernel(rgb_dev dev, const rgb_server_state *__restrict_
   unsigned nr = 0;
   u64 first_index = h.first_index;
   u64 lrs = 0, lrt = 0, prs = 0, prt = 0;
+  bool canonical = true;            /* (an empty table is) */
   if (h.first_index <= h.last_index) {
     unsigned src_n = h.n_runs > RGB_MAX_RUNS ? RGB_MAX_RUNS : h.n_runs;
     /* count canonical runs */
@@ -3922,6 +3958,9 @@ __global__ void rgb_pack_kernel(rgb_dev dev, const rgb_server_state *__restrict_
       if (!(r == 0 || h.run_term[r] != h.run_term[r - 1])) continue;
       if (ci >= skip) {
         if (nr == 0 && skip) first_index = h.run_start[r];
+        /* PK_CANON_SH, verified run by run: run 0 starts at or below first_index, every later run above its
+         * predecessor in start and in term */
+        if (nr == 0 ? h.run_start[r] > first_index : !(h.run_start[r] > lrs && h.run_term[r] > lrt)) canonical = false;
         runs[2 * nr] = h.run_start[r]; runs[2 * nr + 1] = h.run_term[r];
         prs = lrs; prt = lrt;
         lrs = h.run_start[r]; lrt = h.run_term[r];
@@ -3936,6 +3975,7 @@ __global__ void rgb_pack_kernel(rgb_dev dev, const rgb_server_state *__restrict_
   pk = pk_set(pk, PK_SELF_SH, 4, h.self);
   pk = pk_set(pk, PK_VOTES_SH, 4, h.votes);
   pk = pk_set(pk, PK_NRUNS_SH, 5, nr);
+  pk = pk_set(pk, PK_CANON_SH, 1, canonical ? 1 : 0);
   pk = pk_set(pk, PK_NONVOTER_SH, 1, h.self_nonvoter ? 1 : 0);
   pk = pk_set(pk, PK_VOTED_SH, 4, slot8to4(h.voted_for));
   pk = pk_set(pk, PK_LEADER_SH, 4, slot8to4(h.leader_id));
