@@ -19,6 +19,7 @@
          comm_unique_id/0, comm_init/4, allgather_leaderboard/2, node_leaderboard/3]).
 -export([wal_batch_checksums/2, wal_frame/4, wal_recover_check/2, wal_frame_batch/3, wal_recover/2]).
 -export([crc32s/3, crc32_stream/3, segment_build/5, segment_image/4]).
+-export([segment_info/4, segment_compact/6, segment_compact_group/4]).
 -export([encode_msg/3, encode_msgs/1, decode_decision/1, decision_to_effects/3]).
 
 -include_lib("ra/src/ra.hrl").
@@ -148,6 +149,36 @@ wal_recover_check(_Ctx, _FileBin) -> erlang:nif_error(not_loaded).
 crc32s(_Ctx, _EntriesBin, _DataBin) -> erlang:nif_error(not_loaded).
 crc32_stream(_Ctx, _Bin, _Init) -> erlang:nif_error(not_loaded).
 segment_build(_Ctx, _EntriesBin, _DataBin, _MaxCount, _Flags) -> erlang:nif_error(not_loaded).
+
+%% major compaction (src/ra_log_segments.erl:741-835): info/2 of the files of a compaction group, and the new
+%% segment that holds their live entries.  SourcesBin = one 32-byte record per file, little endian:
+%% offset:64, n_bytes:64 (the file inside FilesBin), live_first:32, live_n:32 (its {First, Last} pairs inside
+%% LiveBin), 0:64; LiveBin = First:64/little, Last:64/little per pair, ascending and not adjacent per file.
+%% InfosBin = one 64-byte record per file: size:64, index_size:64, live_size:64, range_first:64, range_last:64,
+%% num_entries:32, num_indexes:32, max_count:32, version:32, status:32, 0:32.  LiveBin = <<>> for segment_info:
+%% no live sequence (`undefined`).
+segment_info(_Ctx, _SourcesBin, _FilesBin, _LiveBin) -> erlang:nif_error(not_loaded).
+segment_compact(_Ctx, _SourcesBin, _FilesBin, _LiveBin, _MaxSize, _Flags) -> erlang:nif_error(not_loaded).
+
+%% Group = [{FileBin, LiveSeq}], oldest file first, LiveSeq the ra_seq:state() of the indexes to keep from that file
+%% (ra_seq:in_range/2 and the progressive ra_seq:limit/2 of src/ra_log_segments.erl:745-761 are the caller's).
+%% -> {ok, SegmentBin}, the bytes ra_log_segment:copy/3 would have left in the new file after the last source
+%% (src/ra_log_segment.erl:819-908), or what copy/3 / append_raw/6 would have failed with:
+%% {error, {copy_missing_key, Idx}} | {error, full} | {error, {truncated | space | crc, SourceNo, Idx}}.
+%% Opening, writing and renaming files, symlinks and compaction markers stay in ra_log_segments.
+segment_compact_group(Ctx, Group, MaxSize, Verify) ->
+    {SourcesBin, Files, LiveBin, _, _} =
+        lists:foldl(fun({FileBin, LiveSeq}, {S, F, L, Off, LiveOff}) ->
+                            Ranges = seq_ranges(LiveSeq),
+                            Len = byte_size(FileBin),
+                            N = length(Ranges),
+                            {<<S/binary, Off:64/little, Len:64/little, LiveOff:32/little, N:32/little, 0:64>>,
+                             [F, FileBin],
+                             << L/binary, << <<Lo:64/little, Hi:64/little>> || {Lo, Hi} <- Ranges >>/binary >>,
+                             Off + Len, LiveOff + N}
+                    end, {<<>>, [], <<>>, 0, 0}, Group),
+    Flags = case Verify of true -> 1; false -> 0 end,
+    segment_compact(Ctx, SourcesBin, iolist_to_binary(Files), LiveBin, MaxSize, Flags).
 
 %% The bytes of a whole segment file for Entries = [{Idx, Term, Bin}] in the caller's order: what
 %% ra_log_segment:append/4 accumulates in pending_index / pending_data and flush/1 writes

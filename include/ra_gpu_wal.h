@@ -228,6 +228,113 @@ int rgb_segment_scan(const void *bytes, uint64_t n_bytes, rgb_seg_entry *out, ui
 int rgb_segment_validate(rgb_ctx *ctx, const void *bytes, uint64_t n_bytes, const rgb_seg_entry *recs,
                          uint32_t n, uint32_t *n_ok);
 
+/* ==== major compaction: what is in a segment file, and the copy of its live entries ======================
+ *
+ * ra_log_segments:major_compaction/3 (src/ra_log_segments.erl:741-835) asks every file of a compaction group what
+ * is in it (ra_log_segment:info/2, src/ra_log_segment.erl:736-790, parse_index_info :1080-1116), opens one new
+ * segment whose MaxCount is the number of live indexes and copies the live entries of every source into it with
+ * ra_log_segment:copy/3 (:819-869), which keeps each entry's stored Crc (append_raw/6, :873-908).
+ *
+ * The index walk of a source (parse_index_data_loop, :1057-1075) reads records from byte 8 until the first all-zero
+ * record, MaxCount records, or the end of the file inside the index region.  The records form a map Idx => entry; a
+ * record whose Idx is smaller than its predecessor's first removes every key greater than its own Idx.  Read in
+ * parallel: record j is in the final map ("effective") iff Idx_j is smaller than every later record's Idx -- the
+ * effective records are strictly ascending in file order, which is the order copy/3 wants (lists:sort of the live
+ * indexes), so nothing is ever sorted.
+ *
+ * Choosing which live indexes belong to which source (ra_seq:in_range/2 and the progressive ra_seq:limit/2 of
+ * src/ra_log_segments.erl:745-761), grouping (take_group, :911-950), file I/O, renames, symlinks and compaction
+ * markers stay with the caller.
+ *
+ * All sources of a group lie in ONE files buffer; the live indexes of all sources in ONE list of (first, last) pairs
+ * of uint64_t (2 * n_live values), each source owning a slice of it.  Within a slice the pairs are ascending and
+ * not adjacent (first <= last, last + 1 < next first): the form rgb_submit_seq takes a ra_seq in.  `sources` and
+ * `live` are HOST arrays in every form: they are validated on the host (a malformed slice, a source outside the
+ * files buffer, too many sources: RGB_E_INVAL, nothing enqueued) and staged by the library.
+ *
+ * The scratch plan of a call lives in the context (released by rgb_close): one info / compact call per context at a
+ * time.  Only a file's own bytes are read, only the new image's own bytes are written, whatever the alignment of
+ * d_files and d_out; payloads move in 16-byte pieces at the payload's own alignment. */
+typedef struct rgb_seg_source {
+  uint64_t offset;       /* the file = files[offset .. offset + n_bytes) */
+  uint64_t n_bytes;
+  uint32_t live_first;   /* this source's live indexes: pairs live_first .. live_first + live_n of the live list */
+  uint32_t live_n;       /* 0: nothing is copied from this source */
+  uint64_t _pad;
+} rgb_seg_source;
+
+/* info/2 of one source (src/ra_log_segment.erl:763-772) */
+typedef struct rgb_seg_info {
+  uint64_t size;          /* Offset + Length of the last record walked; index_size when there is none */
+  uint64_t index_size;    /* data_start = 8 + MaxCount * record size */
+  uint64_t live_size;     /* sum of Length over EVERY walked record whose Idx is live (all records without a live list) */
+  uint64_t range_first;   /* update_range/2 (:919-922): the smallest Idx walked ...            } undefined when        */
+  uint64_t range_last;    /* ... and the Idx of the last record walked                         } num_entries == 0      */
+  uint32_t num_entries;   /* records walked, trimmed and overwritten ones included */
+  uint32_t num_indexes;   /* effective records: ra_seq:length(indexes) */
+  uint32_t max_count;
+  uint32_t version;       /* 1 or 2; 0 with RGB_SEG_COMPACT_BAD_SOURCE */
+  uint32_t status;        /* RGB_SEG_COMPACT_OK or RGB_SEG_COMPACT_BAD_SOURCE */
+  uint32_t _pad;
+} rgb_seg_info;
+
+typedef struct rgb_seg_compact_result {
+  uint32_t status;        /* RGB_SEG_COMPACT_* */
+  uint32_t n_entries;     /* index records written (MaxCount when OK) */
+  uint64_t file_bytes;    /* size of the new image (OK and SPACE) */
+  uint64_t index;         /* MISSING, FULL, TRUNCATED, CRC: the index the status is about */
+  uint32_t source;        /* ... and its source (BAD_SOURCE: the first bad one) */
+  uint32_t _pad;
+} rgb_seg_compact_result;
+
+/* A non-zero status means the reference would have crashed: the contents of the output buffer are then unspecified
+ * (the host-buffer form leaves `out` unwritten).  BAD_SOURCE comes first; then the first entry in copy order (sources
+ * in the caller's order, indexes ascending) that is MISSING, TRUNCATED or FULL, tested in that order; SPACE; and CRC
+ * only when everything else is in order. */
+#define RGB_SEG_COMPACT_OK         0u
+#define RGB_SEG_COMPACT_MISSING    1u  /* exit({copy_missing_key, Idx}) (:864-869): a live index that is not in its source */
+#define RGB_SEG_COMPACT_FULL       2u  /* {error, full} from append_raw: payload bytes already appended > max_size (:1250-1255) */
+#define RGB_SEG_COMPACT_TRUNCATED  3u  /* the payload of a SELECTED record lies outside its file */
+#define RGB_SEG_COMPACT_SPACE      4u  /* out_bytes < file_bytes */
+#define RGB_SEG_COMPACT_CRC        5u  /* RGB_SEG_COMPACT_VERIFY: the first copied payload that does not match its stored Crc */
+#define RGB_SEG_COMPACT_BAD_SOURCE 6u  /* bad magic, fewer than 8 bytes, Version 0 or > 2 (device forms; the host-buffer
+                                          forms see the bytes and answer RGB_E_INVAL) */
+
+#define RGB_SEG_COMPACT_VERIFY      1u    /* flag: CRC-32 of every copied payload in the read that copies it, compared
+                                             with the stored Crc (0 = not checked, validate_checksum/2 :1245-1248).
+                                             Without the flag the copy does no table lookups at all. */
+#define RGB_SEG_COMPACT_MAX_SOURCES 256u
+#define RGB_SEG_MAX_SIZE_DEFAULT    64000000ull   /* ?SEGMENT_MAX_SIZE_B, src/ra.hrl:227 */
+
+/* Host helper, pure: validates the descriptors (as every call below does) and returns through *bound_out
+ * 8 + 32 * MaxCount + the sum of the sources' n_bytes -- always enough for the new image, no device work -- and
+ * through *max_count_out MaxCount = the number of live indexes.  MaxCount > 65535 is RGB_E_INVAL (the header field
+ * has 16 bits); 0 is legal (a header-only 8-byte image).  A caller that has the info rows may size tighter:
+ * 8 + 32 * MaxCount + the sum of live_size. */
+int rgb_segment_compact_bound(const rgb_seg_source *sources, uint32_t n_sources, const uint64_t *live, uint32_t n_live,
+                              uint64_t files_bytes, uint64_t *bound_out, uint32_t *max_count_out);
+
+/* d_infos[s] = info/2 of source s.  live = NULL (n_live = 0): every record counts into live_size and the sources'
+ * slices are ignored.  Enqueued on `stream` (NULL = the context's stream), no synchronisation. */
+int rgb_segment_info_device(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *d_files,
+                            uint64_t files_bytes, const uint64_t *live, uint32_t n_live, void *d_infos, void *stream);
+/* Host-buffer form; a source with a bad header is RGB_E_INVAL. */
+int rgb_segment_info(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *files,
+                     uint64_t files_bytes, const uint64_t *live, uint32_t n_live, rgb_seg_info *infos);
+
+/* d_out[0 .. file_bytes) = the new segment: <<"RASG", 2:16, MaxCount:16>>, the index records of the live entries in
+ * copy order with the SOURCE's stored Crc (0 included) and DataOffsets counted from 8 + 32 * MaxCount, the payloads
+ * back to back.  An index that is live in two sources is copied twice, as the reference does.  *d_result = one
+ * rgb_seg_compact_result in device memory.  max_size: the reference's default is RGB_SEG_MAX_SIZE_DEFAULT.  Unknown
+ * flags: RGB_E_INVAL.  Three launches (four with VERIFY) on `stream`, no synchronisation. */
+int rgb_segment_compact_device(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *d_files,
+                               uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size,
+                               uint32_t flags, void *d_out, uint64_t out_bytes, void *d_result, void *stream);
+/* Host-buffer form: synchronises; `out` is written (its first file_bytes bytes only) when the status is OK. */
+int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *files,
+                        uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size, uint32_t flags,
+                        void *out, uint64_t out_bytes, rgb_seg_compact_result *result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,18 @@ SEG_NO_CHECKSUMS = 1
 SEG_VERSION, SEG_HEADER_BYTES, SEG_RECORD_BYTES, SEG_RECORD_BYTES_V1 = 2, 8, 32, 28
 SEG_END_ZEROS, SEG_END_FULL, SEG_END_TRUNCATED, SEG_END_CAP = 0, 1, 2, 3
 SEG_MAX_ENTRIES, SEG_MAX_SIZE_B = 4096, 64_000_000            # src/ra.hrl:225, 227
+# major compaction (same header): one source file of a group, its info/2 row, the result of the copy
+SEG_SOURCE_DTYPE = np.dtype([("offset", u64), ("n_bytes", u64), ("live_first", u32), ("live_n", u32), ("_pad", u64)])
+SEG_INFO_DTYPE = np.dtype([("size", u64), ("index_size", u64), ("live_size", u64), ("range_first", u64),
+                           ("range_last", u64), ("num_entries", u32), ("num_indexes", u32), ("max_count", u32),
+                           ("version", u32), ("status", u32), ("_pad", u32)])
+SEG_COMPACT_RESULT_DTYPE = np.dtype([("status", u32), ("n_entries", u32), ("file_bytes", u64), ("index", u64),
+                                     ("source", u32), ("_pad", u32)])
+assert (SEG_SOURCE_DTYPE.itemsize, SEG_INFO_DTYPE.itemsize, SEG_COMPACT_RESULT_DTYPE.itemsize) == (32, 64, 32)
+(SEG_COMPACT_OK, SEG_COMPACT_MISSING, SEG_COMPACT_FULL, SEG_COMPACT_TRUNCATED, SEG_COMPACT_SPACE, SEG_COMPACT_CRC,
+ SEG_COMPACT_BAD_SOURCE) = range(7)
+SEG_COMPACT_VERIFY = 1
+SEG_COMPACT_MAX_SOURCES = 256
 
 # rgb_view (ABI v9, rgb_collect_view): pointers into the pinned slot the device wrote
 VIEW_DTYPE = np.dtype([("decisions", "<u8"), ("rpcs", "<u8"), ("tick", "<u8"), ("n", "<u4"), ("n_rpcs", "<u4"),

@@ -733,6 +733,68 @@ static ERL_NIF_TERM nif_segment_build(ErlNifEnv *env, int argc, const ERL_NIF_TE
   return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
 }
 
+/* The descriptors of a compaction group: SourcesBin = n rgb_seg_source records, LiveBin = (first, last) pairs of
+ * native 64-bit unsigned integers.  Their contents are checked by the library (RGB_E_INVAL -> {error, invalid}). */
+static int get_group(ErlNifEnv *env, const ERL_NIF_TERM argv[], nif_ctx **c, ErlNifBinary *s, ErlNifBinary *f,
+                     ErlNifBinary *l) {
+  return get_ctx(env, argv[0], c) && enif_inspect_binary(env, argv[1], s) && enif_inspect_binary(env, argv[2], f) &&
+         enif_inspect_binary(env, argv[3], l) && s->size % sizeof(rgb_seg_source) == 0 && l->size % 16u == 0 &&
+         s->size / sizeof(rgb_seg_source) <= RGB_SEG_COMPACT_MAX_SOURCES && l->size / 16u <= 0xFFFFFFFFu;
+}
+
+/* segment_info(Ctx, SourcesBin, FilesBin, LiveBin) -> {ok, InfosBin}: ra_log_segment:info/2 (src/ra_log_segment.erl:
+ * 736-790) of every source file of FilesBin, one rgb_seg_info record each.  LiveBin = <<>>: no live sequence
+ * (`undefined`), every record counts into live_size. */
+static ERL_NIF_TERM nif_segment_info(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary s, f, l, out;
+  (void)argc;
+  if (!get_group(env, argv, &c, &s, &f, &l)) return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(s.size / sizeof(rgb_seg_source)), n_live = (uint32_t)(l.size / 16u);
+  if (!enif_alloc_binary((size_t)(n ? n : 1) * sizeof(rgb_seg_info), &out)) return mk_error(env, c, RGB_E_NOMEM);
+  int rc = rgb_segment_info(c->ctx, (const rgb_seg_source *)s.data, n, f.data, f.size,
+                            n_live ? (const uint64_t *)l.data : NULL, n_live, (rgb_seg_info *)out.data);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  enif_realloc_binary(&out, (size_t)n * sizeof(rgb_seg_info));
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+}
+
+/* segment_compact(Ctx, SourcesBin, FilesBin, LiveBin, MaxSize, Flags) -> {ok, SegmentBin} |
+ * {error, {copy_missing_key, Idx}} | {error, full} | {error, {truncated | space | crc, Source, Idx}}: the new segment
+ * of a compaction group, ra_log_segment:copy/3 of every source in order (src/ra_log_segment.erl:819-908,
+ * src/ra_log_segments.erl:741-835).  Flags: 1 = check every copied payload against its stored Crc. */
+static ERL_NIF_TERM nif_segment_compact(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary s, f, l, out; uint64_t max_size, bound = 0; unsigned flags; uint32_t max_count = 0;
+  (void)argc;
+  if (!get_group(env, argv, &c, &s, &f, &l) || !enif_get_uint64(env, argv[4], &max_size) ||
+      !enif_get_uint(env, argv[5], &flags))
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(s.size / sizeof(rgb_seg_source)), n_live = (uint32_t)(l.size / 16u);
+  const rgb_seg_source *sources = (const rgb_seg_source *)s.data;
+  const uint64_t *live = n_live ? (const uint64_t *)l.data : NULL;
+  int rc = rgb_segment_compact_bound(sources, n, live, n_live, f.size, &bound, &max_count);
+  if (rc) return mk_error(env, c, rc);
+  if (!enif_alloc_binary((size_t)bound, &out)) return mk_error(env, c, RGB_E_NOMEM);
+  rgb_seg_compact_result res;
+  rc = rgb_segment_compact(c->ctx, sources, n, f.data, f.size, live, n_live, max_size, flags, out.data, bound, &res);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  if (res.status == RGB_SEG_COMPACT_OK) {
+    enif_realloc_binary(&out, (size_t)res.file_bytes);
+    return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+  }
+  enif_release_binary(&out);
+  ERL_NIF_TERM why;
+  if (res.status == RGB_SEG_COMPACT_MISSING)
+    why = enif_make_tuple2(env, enif_make_atom(env, "copy_missing_key"), enif_make_uint64(env, res.index));
+  else if (res.status == RGB_SEG_COMPACT_FULL)
+    why = enif_make_atom(env, "full");
+  else
+    why = enif_make_tuple3(env, enif_make_atom(env, res.status == RGB_SEG_COMPACT_TRUNCATED ? "truncated" :
+                                                    res.status == RGB_SEG_COMPACT_SPACE ? "space" :
+                                                    res.status == RGB_SEG_COMPACT_CRC ? "crc" : "bad_source"),
+                           enif_make_uint(env, res.source), enif_make_uint64(env, res.index));
+  return enif_make_tuple2(env, enif_make_atom(env, "error"), why);
+}
+
 static ErlNifFunc nif_funcs[] = {
   {"open", 4, nif_open, 0},
   {"register_groups", 3, nif_register_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
@@ -759,6 +821,8 @@ static ErlNifFunc nif_funcs[] = {
   {"crc32s", 3, nif_crc32s, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"crc32_stream", 3, nif_crc32_stream, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_build", 5, nif_segment_build, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_info", 4, nif_segment_info, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_compact", 6, nif_segment_compact, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(ra_gpu_batch, nif_funcs, on_load, NULL, NULL, NULL)

@@ -4,6 +4,8 @@
  *   - per-entry CRC of a batch of payloads          (src/ra_log_segment.erl:277, 670, 1240-1248)
  *   - the whole segment file image in one pass      (src/ra_log_segment.erl:1118-1122, 1211-1219)
  *   - one long buffer with a starting value         (src/ra_log_snapshot.erl:57-107, 256; src/ra_snapshot.erl:1020, 1038)
+ * and, behind them, major compaction: info/2 of the files of a group and the copy of their live entries into one new
+ * segment (src/ra_log_segment.erl:736-790, 819-908; src/ra_log_segments.erl:741-835) -- "major compaction" below.
  *
  * The arithmetic.  With a ZERO register and no final xor the CRC is linear over GF(2): raw(M) = M(x) * x^32 mod P,
  *     raw(A ++ B) = raw(A) * x^(8 |B|)  xor  raw(B),        raw(zeros ++ M) = raw(M)
@@ -324,6 +326,336 @@ __global__ __launch_bounds__(THREADS) void rgb_seg_combine_kernel(const u32 *__r
   }
 }
 
+/* ---- major compaction (include/ra_gpu_wal.h, "major compaction") -------------------------------------------
+ * Three passes, each its own launch, so that no workgroup ever waits for another:
+ *   resolve  one workgroup per source: the index walk, which records are effective, which of those are live; the info
+ *            row, the source's counters and one plan record per selected entry, in copy order
+ *   place    one thread: the sources' bases, file_bytes, the first MISSING / TRUNCATED / FULL entry in copy order, SPACE
+ *   copy     GROUP lanes per plan record: the payload (with or without its CRC), the index record; nothing at all
+ *            unless the status is OK
+ * When the status is OK every live index was found, so the plan is dense, its position IS the record number of the new
+ * file, and MaxCount records are written: there are no unused index records to zero.
+ * The kernels' parameter types are the unit's own (the resource gate of tests/test_segment.py counts kernels by the
+ * header's type prefix in their symbol names). */
+constexpr u32 NONE32 = 0xFFFFFFFFu;
+constexpr u64 NONE64 = ~0ull;
+constexpr u32 CMP_MAX_RECORDS = 65536u;         /* MaxCount has 16 bits */
+
+struct src_desc { u64 offset, n_bytes; u32 live_first, live_n, asked, plan_base; };        /* staged from the host */
+struct src_done { u64 sel_bytes, miss_idx; u32 sel_count, miss_k, trunc_k, bad; };         /* resolve -> place */
+struct alignas(16) plan_rec { u64 idx, term, src_off, pre; u32 len, crc, src, _pad; };     /* resolve -> place, copy */
+struct work_hdr { u32 status, crc_fail, _pad[2]; };                                        /* place -> copy -> finish */
+static_assert(sizeof(src_desc) == 32 && sizeof(src_done) == 32 && sizeof(plan_rec) == 48 && sizeof(work_hdr) == 16, "");
+
+__device__ __forceinline__ void atomic_min(u32 *p, u32 v) {
+  u32 old = *p;
+  while (v < old) {
+    const u32 seen = atomicCAS(p, old, v);
+    if (seen == old) break;
+    old = seen;
+  }
+}
+__device__ __forceinline__ u64 ld_be64(const unsigned char *p) { u64 v; __builtin_memcpy(&v, p, 8); return __builtin_bswap64(v); }
+__device__ __forceinline__ u32 ld_be32(const unsigned char *p) { u32 v; __builtin_memcpy(&v, p, 4); return __builtin_bswap32(v); }
+
+struct idx_rec { u64 idx, term, off; u32 len, crc; };
+/* decode_index_record/3 (src/ra_log_segment.erl:1180-1209) */
+__device__ __forceinline__ idx_rec decode_rec(const unsigned char *p, bool v2) {
+  idx_rec r;
+  r.idx = ld_be64(p); r.term = ld_be64(p + 8);
+  r.off = v2 ? ld_be64(p + 16) : (u64)ld_be32(p + 16);
+  r.len = ld_be32(p + (v2 ? 24 : 20)); r.crc = ld_be32(p + (v2 ? 28 : 24));
+  return r;
+}
+/* ra_seq:in/2 over pairs [first, first + n) of the live list; *which = the pair that holds idx */
+__device__ __forceinline__ bool live_find(const u64 *live, u32 first, u32 n, u64 idx, u32 *which) {
+  u32 lo = 0, hi = n;                                   /* lo = pairs whose first <= idx */
+  while (lo < hi) {
+    const u32 mid = (lo + hi) >> 1;
+    if (live[2 * (u64)(first + mid)] <= idx) lo = mid + 1u; else hi = mid;
+  }
+  if (!lo) return false;
+  *which = first + lo - 1u;
+  return idx <= live[2 * (u64)*which + 1u];
+}
+
+__global__ __launch_bounds__(THREADS) void rgb_compact_resolve_kernel(
+    const src_desc *__restrict__ srcs, const unsigned char *__restrict__ files, const u64 *__restrict__ live,
+    const u32 *__restrict__ rank, u32 all_live, void *infos_v, src_done *__restrict__ done, plan_rec *__restrict__ plan) {
+  __shared__ u64 s_wide[THREADS];                       /* scan buffer: suffix min of Idx, prefix sum of bytes */
+  __shared__ u32 s_cnt[THREADS];                        /* scan buffer: prefix count */
+  __shared__ u32 s_bits[CMP_MAX_RECORDS / 32];          /* record j is effective */
+  __shared__ u32 s_first_zero, s_eff, s_miss_k, s_trunc_k;
+  __shared__ u64 s_live_size;
+  const u32 tid = threadIdx.x, s = blockIdx.x;
+  const src_desc sd = srcs[s];
+  const unsigned char *f = files + sd.offset;
+  rgb_seg_info *info = infos_v ? reinterpret_cast<rgb_seg_info *>(infos_v) + s : nullptr;
+
+  /* read_header/1 (:1124-1138) */
+  u32 version = 0, max_count = 0;
+  if (sd.n_bytes >= RGB_SEG_HEADER_BYTES && f[0] == 'R' && f[1] == 'A' && f[2] == 'S' && f[3] == 'G') {
+    version = ((u32)f[4] << 8) | f[5];
+    max_count = ((u32)f[6] << 8) | f[7];
+  }
+  if (version < 1u || version > RGB_SEG_VERSION) {      /* the same for every lane */
+    if (tid == 0u) {
+      if (info) { rgb_seg_info z{}; z.status = RGB_SEG_COMPACT_BAD_SOURCE; *info = z; }
+      if (done) { src_done d{}; d.miss_k = d.trunc_k = NONE32; d.bad = 1u; done[s] = d; }
+    }
+    return;
+  }
+  const bool v2 = version == 2u;
+  const u32 rec_bytes = v2 ? RGB_SEG_RECORD_BYTES : RGB_SEG_RECORD_BYTES_V1;
+  const u64 data_start = (u64)RGB_SEG_HEADER_BYTES + (u64)rec_bytes * max_count;
+  const u64 fit = (sd.n_bytes - RGB_SEG_HEADER_BYTES) / rec_bytes;            /* whole records inside the file */
+  const u32 n_fit = fit < max_count ? (u32)fit : max_count;
+  const unsigned char *index = f + RGB_SEG_HEADER_BYTES;
+
+  /* pass A: where the walk ends -- the first all-zero record */
+  if (tid == 0u) { s_first_zero = n_fit; s_eff = 0u; s_miss_k = NONE32; s_trunc_k = NONE32; s_live_size = 0ull; }
+  for (u32 i = tid; i < CMP_MAX_RECORDS / 32; i += THREADS) s_bits[i] = 0u;
+  __syncthreads();
+  for (u32 base = 0; base < n_fit; base += THREADS) {
+    const u32 j = base + tid;
+    if (j < n_fit) {
+      const idx_rec r = decode_rec(index + (u64)rec_bytes * j, v2);
+      if ((r.idx | r.term | r.off | r.len | r.crc) == 0ull) atomic_min(&s_first_zero, j);
+    }
+    __syncthreads();
+    const u32 z = s_first_zero;
+    __syncthreads();
+    if (z != n_fit) break;
+  }
+  const u32 n_walk = s_first_zero;
+  const u32 n_chunks = (n_walk + THREADS - 1u) / THREADS;
+
+  /* pass B, last chunk first: record j is effective iff Idx_j < min Idx of every later record (the last one always
+   * is) -- a reverse exclusive min-scan, `carry` the minimum of the chunks already seen */
+  u64 carry = NONE64, my_live = 0;
+  for (u32 c = n_chunks; c-- > 0u;) {
+    const u32 j = c * THREADS + tid;
+    const bool valid = j < n_walk;
+    idx_rec r{};
+    if (valid) r = decode_rec(index + (u64)rec_bytes * j, v2);
+    s_wide[tid] = valid ? r.idx : NONE64;
+    __syncthreads();
+    for (u32 off = 1; off < THREADS; off <<= 1) {
+      u64 t = s_wide[tid];
+      if (tid + off < THREADS && s_wide[tid + off] < t) t = s_wide[tid + off];
+      __syncthreads();
+      s_wide[tid] = t;
+      __syncthreads();
+    }
+    u64 later = tid + 1u < THREADS ? s_wide[tid + 1u] : NONE64;
+    if (carry < later) later = carry;
+    const u64 chunk_min = s_wide[0];
+    if (valid && (j == n_walk - 1u || r.idx < later)) {
+      atomicOr(&s_bits[j >> 5], 1u << (j & 31u));
+      atomicAdd(&s_eff, 1u);
+    }
+    u32 which;
+    if (valid && (all_live || live_find(live, sd.live_first, sd.live_n, r.idx, &which))) my_live += r.len;
+    if (chunk_min < carry) carry = chunk_min;
+    __syncthreads();
+  }
+  if (my_live) atomicAdd(&s_live_size, (unsigned long long)my_live);
+  __syncthreads();
+
+  if (info && tid == 0u) {
+    rgb_seg_info o{};
+    o.size = o.index_size = data_start;
+    if (n_walk) {
+      const idx_rec last = decode_rec(index + (u64)rec_bytes * (n_walk - 1u), v2);
+      o.size = last.off + last.len;
+      o.range_first = carry; o.range_last = last.idx;
+    }
+    o.live_size = s_live_size;
+    o.num_entries = n_walk; o.num_indexes = s_eff; o.max_count = max_count; o.version = version;
+    o.status = RGB_SEG_COMPACT_OK;
+    *info = o;
+  }
+  if (!done) return;
+
+  /* pass C, in file order: the selected records (effective and live) get their place in the source's part of the
+   * plan and their running byte offset; a selected record whose rank among the source's live indexes is not its
+   * place has a missing index in front of it */
+  u32 run_cnt = 0;
+  u64 run_bytes = 0;
+  for (u32 c = 0; c < n_chunks; ++c) {
+    const u32 j = c * THREADS + tid;
+    idx_rec r{};
+    u32 which = 0;
+    bool sel = j < n_walk && ((s_bits[j >> 5] >> (j & 31u)) & 1u);
+    if (sel) {
+      r = decode_rec(index + (u64)rec_bytes * j, v2);
+      sel = live_find(live, sd.live_first, sd.live_n, r.idx, &which);
+    }
+    s_cnt[tid] = sel ? 1u : 0u;
+    s_wide[tid] = sel ? (u64)r.len : 0ull;
+    __syncthreads();
+    for (u32 off = 1; off < THREADS; off <<= 1) {
+      u32 tc = s_cnt[tid];
+      u64 tb = s_wide[tid];
+      if (tid >= off) { tc += s_cnt[tid - off]; tb += s_wide[tid - off]; }
+      __syncthreads();
+      s_cnt[tid] = tc; s_wide[tid] = tb;
+      __syncthreads();
+    }
+    if (sel) {
+      const u32 k = run_cnt + s_cnt[tid] - 1u;
+      if (k < sd.asked) {
+        plan_rec p;
+        p.idx = r.idx; p.term = r.term; p.src_off = sd.offset + r.off; p.pre = run_bytes + s_wide[tid] - r.len;
+        p.len = r.len; p.crc = r.crc; p.src = s; p._pad = 0u;
+        plan[sd.plan_base + k] = p;
+      }
+      if (rank[which] + (u32)(r.idx - live[2 * (u64)which]) != k) atomic_min(&s_miss_k, k);
+      if (r.off > sd.n_bytes || r.len > sd.n_bytes - r.off) atomic_min(&s_trunc_k, k);
+    }
+    run_cnt += s_cnt[THREADS - 1];
+    run_bytes += s_wide[THREADS - 1];
+    __syncthreads();
+  }
+  if (tid == 0u) {
+    src_done d{};
+    d.sel_bytes = run_bytes; d.sel_count = run_cnt; d.trunc_k = s_trunc_k; d.miss_k = s_miss_k;
+    if (d.miss_k == NONE32 && run_cnt < sd.asked) d.miss_k = run_cnt;
+    if (d.miss_k != NONE32) {                           /* the live index of rank miss_k */
+      u32 lo = 0, hi = sd.live_n;                       /* lo = pairs whose rank <= miss_k; at least one */
+      while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (rank[sd.live_first + mid] <= d.miss_k) lo = mid + 1u; else hi = mid;
+      }
+      const u32 i = sd.live_first + lo - 1u;
+      d.miss_idx = live[2 * (u64)i] + (d.miss_k - rank[i]);
+    }
+    done[s] = d;
+  }
+}
+
+__global__ void rgb_compact_place_kernel(const src_desc *__restrict__ srcs, u32 n_sources, const src_done *__restrict__ done,
+                                         const plan_rec *__restrict__ plan, u32 max_count, u64 max_size, u64 out_bytes,
+                                         u64 *__restrict__ byte_base, work_hdr *__restrict__ hdr, void *result_v) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  rgb_seg_compact_result res{};
+  u64 bytes = 0;
+  u32 recs = 0;
+  for (u32 s = 0; s < n_sources && !res.status; ++s)
+    if (done[s].bad) { res.status = RGB_SEG_COMPACT_BAD_SOURCE; res.source = s; }
+  for (u32 s = 0; s < n_sources && !res.status; ++s) {
+    const src_done d = done[s];
+    const plan_rec *p = plan + srcs[s].plan_base;
+    /* append_raw refuses entry k when the payload bytes in front of it exceed max_size (is_full/1, :1250-1255) */
+    u32 full_k = NONE32;
+    if (d.sel_count && bytes + p[d.sel_count - 1u].pre > max_size) {
+      u32 lo = 0, hi = d.sel_count - 1u;                /* the first k with bytes + pre[k] > max_size */
+      while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (bytes + p[mid].pre > max_size) hi = mid; else lo = mid + 1u;
+      }
+      full_k = lo;
+    }
+    /* copy order: the missing index is met before the entry that took its place; the payload is read before append_raw */
+    if (d.miss_k != NONE32 && d.miss_k <= d.trunc_k && d.miss_k <= full_k) {
+      res.status = RGB_SEG_COMPACT_MISSING; res.source = s; res.index = d.miss_idx;
+    } else if (d.trunc_k != NONE32 && d.trunc_k <= full_k) {
+      res.status = RGB_SEG_COMPACT_TRUNCATED; res.source = s; res.index = p[d.trunc_k].idx;
+    } else if (full_k != NONE32) {
+      res.status = RGB_SEG_COMPACT_FULL; res.source = s; res.index = p[full_k].idx;
+    } else {
+      byte_base[s] = bytes;
+      bytes += d.sel_bytes;
+      recs += d.sel_count;
+    }
+  }
+  if (!res.status) {
+    res.n_entries = recs;                               /* == max_count: every live index was found */
+    res.file_bytes = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * max_count + bytes;
+    if (out_bytes < res.file_bytes) { res.status = RGB_SEG_COMPACT_SPACE; res.n_entries = 0u; }
+  }
+  hdr->status = res.status;
+  hdr->crc_fail = NONE32;
+  __builtin_memcpy(result_v, &res, sizeof res);
+}
+
+/* plain gather-copy of a payload of len >= 16 bytes: 16-byte slots aligned to its END (as load_slot), the first one
+ * moved up to the payload's start -- the bytes it shares with its successor are written twice with the same value */
+template <int GROUP>
+__device__ __forceinline__ void copy_plain(const unsigned char *pay, unsigned char *dst, u32 len, u32 lane) {
+  const u32 slots = (u32)(((u64)len + 15u) >> 4);
+  const u32 pad = (u32)(((u64)slots << 4) - len);
+#pragma unroll 4
+  for (u32 t = lane; t < slots; t += (u32)GROUP) {
+    const u64 q = t ? ((u64)t << 4) - pad : 0ull;
+    *reinterpret_cast<v4u_any *>(dst + q) = __builtin_nontemporal_load(reinterpret_cast<const v4u_any *>(pay + q));
+  }
+}
+
+template <int GROUP, bool VERIFY>
+__global__ __launch_bounds__(THREADS) void rgb_compact_copy_kernel(
+    const plan_rec *__restrict__ plan, u32 n, const unsigned char *__restrict__ files, const u64 *__restrict__ byte_base,
+    work_hdr *__restrict__ hdr, unsigned char *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) u32 lds[VERIFY ? LDS_WORDS : 4u];
+  if (hdr->status != RGB_SEG_COMPACT_OK) return;        /* decided before this launch: the same for every lane */
+  if (VERIFY) load_tables<GROUP>(lds);
+  constexpr u32 PER_BLOCK = THREADS / GROUP;
+  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
+  const u32 lane = threadIdx.x & (GROUP - 1);
+  const u64 data_start = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * n;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    struct __attribute__((packed)) hdr8 { u64 v; } h;
+    h.v = 0x47534152ull | (0x0200ull << 32) | ((u64)((n >> 8) & 0xFFu) << 48) | ((u64)(n & 0xFFu) << 56);
+    __builtin_memcpy(out, &h, 8);
+  }
+  for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
+    const u32 e = base + threadIdx.x / GROUP;
+    const bool live = e < n;
+    plan_rec p{};
+    u64 dst_off = 0;
+    if (live) { p = plan[e]; dst_off = data_start + byte_base[p.src] + p.pre; }
+    const u32 len = p.len;
+    const unsigned char *pay = files + p.src_off;
+    unsigned char *dst = out + dst_off;
+    const bool wide = live && len >= 16u;
+    u32 crc = 0;
+    if (VERIFY) {
+      const u32 part = lane_raw<GROUP, UNROLL, true>(lds, pay, dst, wide ? len : 0u, lane, 0xFFFFFFFFu);
+      crc = ~group_xor<GROUP>(part);
+    } else if (wide) {
+      copy_plain<GROUP>(pay, dst, len, lane);
+    }
+    if (live && lane == 0u) {
+      if (!wide) {
+        if (VERIFY) crc = crc_bytes(lds, 0u, pay, len, dst);
+        else for (u32 k = 0; k < len; ++k) dst[k] = pay[k];
+      }
+      if (VERIFY && p.crc != 0u && crc != p.crc) atomic_min(&hdr->crc_fail, e);
+      v4u a, b;
+      a.x = __builtin_bswap32((u32)(p.idx >> 32));   a.y = __builtin_bswap32((u32)p.idx);
+      a.z = __builtin_bswap32((u32)(p.term >> 32));  a.w = __builtin_bswap32((u32)p.term);
+      b.x = __builtin_bswap32((u32)(dst_off >> 32)); b.y = __builtin_bswap32((u32)dst_off);
+      b.z = __builtin_bswap32(len);                  b.w = __builtin_bswap32(p.crc);      /* the source's Crc, 0 included */
+      unsigned char *rec = out + RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * e;
+      *reinterpret_cast<v4u_any *>(rec) = a;
+      *reinterpret_cast<v4u_any *>(rec + 16) = b;
+    }
+  }
+}
+
+/* VERIFY: the first mismatch in copy order, once every workgroup of the copy is done */
+__global__ void rgb_compact_finish_kernel(const plan_rec *__restrict__ plan, const work_hdr *__restrict__ hdr, void *result_v) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  if (hdr->status != RGB_SEG_COMPACT_OK || hdr->crc_fail == NONE32) return;
+  rgb_seg_compact_result res;
+  __builtin_memcpy(&res, result_v, sizeof res);
+  res.status = RGB_SEG_COMPACT_CRC;
+  res.n_entries = 0u;
+  res.source = plan[hdr->crc_fail].src;
+  res.index = plan[hdr->crc_fail].idx;
+  __builtin_memcpy(result_v, &res, sizeof res);
+}
+
 /* x^(8 n) mod P on the host */
 inline u32 host_xpow8(u64 n) { return xpow8_c(n); }
 
@@ -336,6 +668,7 @@ extern "C" void *rgb_ctx_stream(rgb_ctx *ctx);
 extern "C" int rgb_ctx_device(rgb_ctx *ctx);
 
 /* ---- per-context device buffers: staging of the host-buffer forms, partial values of the stream form ---- */
+#include <string.h>
 #include <mutex>
 #include <memory>
 #include <unordered_map>
@@ -346,6 +679,12 @@ struct stage {
   void *d_entries = nullptr, *d_data = nullptr, *d_crcs = nullptr, *d_offsets = nullptr, *d_out = nullptr;
   size_t cap_e = 0, cap_d = 0, cap_c = 0, cap_o = 0, cap_out = 0;
   void *d_partials = nullptr;     /* STREAM_MAX_BLOCKS values + the one result of the host-buffer form */
+  /* compaction: the descriptors of a call (pinned, and their device copy), the scratch plan, the result of the
+   * host-buffer form; `staged` is recorded behind the upload, the next call waits for it before it refills h_desc */
+  void *h_desc = nullptr, *d_desc = nullptr, *d_work = nullptr, *d_result = nullptr;
+  size_t cap_hdesc = 0, cap_desc = 0, cap_work = 0, cap_result = 0;
+  hipEvent_t staged = nullptr;
+  bool staged_recorded = false;
 };
 std::recursive_mutex g_mu;     /* the host-buffer forms call the device forms with it held */
 std::unordered_map<rgb_ctx *, stage> g_stages;
@@ -374,8 +713,10 @@ extern "C" void rgb_seg_release(rgb_ctx *ctx) {      /* called by rgb_close */
   auto it = seg::g_stages.find(ctx);
   if (it == seg::g_stages.end()) return;
   seg::stage &s = it->second;
-  void *all[] = {s.d_entries, s.d_data, s.d_crcs, s.d_offsets, s.d_out, s.d_partials};
+  void *all[] = {s.d_entries, s.d_data, s.d_crcs, s.d_offsets, s.d_out, s.d_partials, s.d_desc, s.d_work, s.d_result};
   for (void *p : all) if (p) (void)hipFree(p);
+  if (s.h_desc) (void)hipHostFree(s.h_desc);
+  if (s.staged) (void)hipEventDestroy(s.staged);
   seg::g_stages.erase(it);
 }
 
@@ -540,5 +881,220 @@ extern "C" int rgb_segment_validate(rgb_ctx *ctx, const void *bytes, uint64_t n_
   if (rc) return rc;
   for (uint32_t i = 0; i < n; ++i)
     if (recs[i].crc != 0u && recs[i].crc != sums[i]) { *n_ok = i; break; }
+  return RGB_OK;
+}
+
+/* ---- major compaction: info/2 and copy/3 of a compaction group ------------------------------------------- */
+
+extern "C" int rgb_seg_compact_check(const rgb_seg_source *sources, uint32_t n_sources, const uint64_t *live,
+                                     uint32_t n_live, uint64_t files_bytes, int with_live, int limit_count,
+                                     uint32_t *asked, uint32_t *rank, uint64_t *sum_bytes, uint32_t *max_count);
+
+namespace {
+namespace seg {
+struct staged_call {
+  const src_desc *d_srcs = nullptr;
+  const u64 *d_live = nullptr;
+  const u32 *d_rank = nullptr;
+  src_done *d_done = nullptr;
+  u64 *d_byte_base = nullptr;
+  work_hdr *d_hdr = nullptr;
+  plan_rec *d_plan = nullptr;
+  u32 max_count = 0;
+  u64 sum_bytes = 0;
+};
+inline size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+/* Validate the descriptors, put them (and the live list, and its ranks) behind each other in the context's pinned
+ * buffer, upload that on `st`, size the scratch plan.  compact = false: the info form, no counts, no plan. */
+int stage_call(stage &s, const rgb_seg_source *sources, u32 n_sources, const uint64_t *live, u32 n_live,
+               uint64_t files_bytes, bool with_live, bool compact, hipStream_t st, staged_call *out) {
+  const size_t off_live = (size_t)n_sources * sizeof(src_desc);
+  const size_t off_rank = off_live + (size_t)n_live * 16u;
+  const size_t need = up16(off_rank + (size_t)n_live * 4u) + 16u;
+  if (!s.staged && hipEventCreateWithFlags(&s.staged, hipEventDisableTiming) != hipSuccess) return RGB_E_HIP;
+  if (s.staged_recorded && hipEventSynchronize(s.staged) != hipSuccess) return RGB_E_HIP;
+  s.staged_recorded = false;
+  if (need > s.cap_hdesc) {
+    if (s.h_desc) (void)hipHostFree(s.h_desc);
+    s.h_desc = nullptr; s.cap_hdesc = 0;
+    if (hipHostMalloc(&s.h_desc, need * 2u, hipHostMallocDefault) != hipSuccess) return RGB_E_NOMEM;
+    s.cap_hdesc = need * 2u;
+  }
+  unsigned char *h = (unsigned char *)s.h_desc;
+  src_desc *h_srcs = (src_desc *)h;
+  u32 *h_rank = (u32 *)(h + off_rank);
+  uint32_t asked[RGB_SEG_COMPACT_MAX_SOURCES];
+  uint32_t max_count = 0;
+  uint64_t sum = 0;
+  const int rc = rgb_seg_compact_check(sources, n_sources, live, n_live, files_bytes, with_live ? 1 : 0, compact ? 1 : 0,
+                                       asked, h_rank, &sum, &max_count);
+  if (rc) return rc;
+  u32 plan_base = 0;
+  for (u32 i = 0; i < n_sources; ++i) {
+    src_desc d;
+    d.offset = sources[i].offset; d.n_bytes = sources[i].n_bytes;
+    d.live_first = with_live ? sources[i].live_first : 0u; d.live_n = with_live ? sources[i].live_n : 0u;
+    d.asked = compact ? asked[i] : 0u; d.plan_base = plan_base;
+    plan_base += d.asked;
+    h_srcs[i] = d;
+  }
+  if (n_live && with_live) memcpy(h + off_live, live, (size_t)n_live * 16u);
+  const size_t off_base = (size_t)n_sources * sizeof(src_done);
+  const size_t off_hdr = up16(off_base + (size_t)n_sources * 8u);
+  const size_t off_plan = off_hdr + sizeof(work_hdr);
+  if (grow(&s.d_desc, &s.cap_desc, need) || grow(&s.d_work, &s.cap_work, off_plan + (size_t)max_count * sizeof(plan_rec) + 16u))
+    return RGB_E_NOMEM;
+  if (hipMemcpyAsync(s.d_desc, s.h_desc, need, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  if (hipEventRecord(s.staged, st) != hipSuccess) return RGB_E_HIP;
+  s.staged_recorded = true;
+  unsigned char *d = (unsigned char *)s.d_desc, *w = (unsigned char *)s.d_work;
+  out->d_srcs = (const src_desc *)d;
+  out->d_live = (const u64 *)(d + off_live);
+  out->d_rank = (const u32 *)(d + off_rank);
+  out->d_done = (src_done *)w;
+  out->d_byte_base = (u64 *)(w + off_base);
+  out->d_hdr = (work_hdr *)(w + off_hdr);
+  out->d_plan = (plan_rec *)(w + off_plan);
+  out->max_count = max_count;
+  out->sum_bytes = sum;
+  return RGB_OK;
+}
+
+/* what the host-buffer forms answer RGB_E_INVAL to, where the device forms report RGB_SEG_COMPACT_BAD_SOURCE */
+bool headers_ok(const rgb_seg_source *sources, u32 n_sources, const unsigned char *files) {
+  for (u32 i = 0; i < n_sources; ++i) {
+    const unsigned char *f = files + sources[i].offset;
+    if (sources[i].n_bytes < RGB_SEG_HEADER_BYTES || f[0] != 'R' || f[1] != 'A' || f[2] != 'S' || f[3] != 'G') return false;
+    const u32 version = ((u32)f[4] << 8) | f[5];
+    if (version < 1u || version > RGB_SEG_VERSION) return false;
+  }
+  return true;
+}
+}  // namespace seg
+}  // namespace
+
+extern "C" int rgb_segment_info_device(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *d_files,
+                                       uint64_t files_bytes, const uint64_t *live, uint32_t n_live, void *d_infos,
+                                       void *stream) {
+  if (!ctx || (n_sources && (!sources || !d_infos)) || (files_bytes && !d_files) || (n_live && !live)) return RGB_E_INVAL;
+  if (n_sources > RGB_SEG_COMPACT_MAX_SOURCES) return RGB_E_INVAL;
+  if (n_sources == 0) return RGB_OK;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  seg::staged_call c;
+  const bool with_live = live != nullptr;
+  int rc = seg::stage_call(s, sources, n_sources, live, with_live ? n_live : 0u, files_bytes, with_live, false, st, &c);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(seg::rgb_compact_resolve_kernel, dim3(n_sources), dim3(seg::THREADS), 0, st, c.d_srcs,
+                     (const unsigned char *)d_files, c.d_live, (const seg::u32 *)nullptr, with_live ? 0u : 1u, d_infos,
+                     (seg::src_done *)nullptr, (seg::plan_rec *)nullptr);
+  return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_segment_compact_device(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources,
+                                          const void *d_files, uint64_t files_bytes, const uint64_t *live, uint32_t n_live,
+                                          uint64_t max_size, uint32_t flags, void *d_out, uint64_t out_bytes,
+                                          void *d_result, void *stream) {
+  if (!ctx || !d_out || !d_result || (n_sources && !sources) || (files_bytes && !d_files) || (n_live && !live) ||
+      (flags & ~RGB_SEG_COMPACT_VERIFY))
+    return RGB_E_INVAL;
+  if (n_sources > RGB_SEG_COMPACT_MAX_SOURCES) return RGB_E_INVAL;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  seg::staged_call c;
+  int rc = seg::stage_call(s, sources, n_sources, live, n_live, files_bytes, true, true, st, &c);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  if (n_sources)
+    hipLaunchKernelGGL(seg::rgb_compact_resolve_kernel, dim3(n_sources), dim3(seg::THREADS), 0, st, c.d_srcs,
+                       (const unsigned char *)d_files, c.d_live, c.d_rank, 0u, (void *)nullptr, c.d_done, c.d_plan);
+  hipLaunchKernelGGL(seg::rgb_compact_place_kernel, dim3(1), dim3(64), 0, st, c.d_srcs, n_sources,
+                     (const seg::src_done *)c.d_done, (const seg::plan_rec *)c.d_plan, c.max_count, (seg::u64)max_size,
+                     (seg::u64)out_bytes, c.d_byte_base, c.d_hdr, d_result);
+  /* the lane-group width of rgb_segment_build_device, from what the host knows without a sync: a wrong guess costs
+   * speed, never correctness */
+  const uint32_t n = c.max_count;
+  const uint64_t mean = c.sum_bytes / (n ? n : 1u);
+  const bool verify = (flags & RGB_SEG_COMPACT_VERIFY) != 0u;
+#define SEG_COPY_LAUNCH(G, V)                                                                                        \
+  do {                                                                                                               \
+    const seg::u32 per = seg::THREADS / (G);                                                                         \
+    seg::u32 grid = (n + per - 1) / per;                                                                             \
+    if (grid > seg::GRID_CAP) grid = seg::GRID_CAP;                                                                  \
+    if (grid == 0) grid = 1;                                                                                         \
+    hipLaunchKernelGGL((seg::rgb_compact_copy_kernel<G, V>), dim3(grid), dim3(seg::THREADS), 0, st,                  \
+                       (const seg::plan_rec *)c.d_plan, n, (const unsigned char *)d_files,                           \
+                       (const seg::u64 *)c.d_byte_base, c.d_hdr, (unsigned char *)d_out);                            \
+  } while (0)
+  if (verify) {
+    if (mean <= 320u) SEG_COPY_LAUNCH(8, true);
+    else if (mean < 1024u) SEG_COPY_LAUNCH(16, true);
+    else SEG_COPY_LAUNCH(64, true);
+    hipLaunchKernelGGL(seg::rgb_compact_finish_kernel, dim3(1), dim3(64), 0, st, (const seg::plan_rec *)c.d_plan,
+                       (const seg::work_hdr *)c.d_hdr, d_result);
+  } else {
+    if (mean <= 320u) SEG_COPY_LAUNCH(8, false);
+    else if (mean < 1024u) SEG_COPY_LAUNCH(16, false);
+    else SEG_COPY_LAUNCH(64, false);
+  }
+#undef SEG_COPY_LAUNCH
+  return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_segment_info(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *files,
+                                uint64_t files_bytes, const uint64_t *live, uint32_t n_live, rgb_seg_info *infos) {
+  if (!ctx || (n_sources && (!sources || !infos)) || (files_bytes && !files) || (n_live && !live)) return RGB_E_INVAL;
+  int rc = rgb_seg_compact_check(sources, n_sources, live, live ? n_live : 0u, files_bytes, live ? 1 : 0, 0, nullptr,
+                                 nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  if (!seg::headers_ok(sources, n_sources, (const unsigned char *)files)) return RGB_E_INVAL;
+  if (n_sources == 0) return RGB_OK;
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  const size_t need_i = (size_t)n_sources * sizeof(rgb_seg_info);
+  if (seg::grow(&s.d_data, &s.cap_d, (size_t)files_bytes) || seg::grow(&s.d_result, &s.cap_result, need_i)) return RGB_E_NOMEM;
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (files_bytes && hipMemcpyAsync(s.d_data, files, files_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  rc = rgb_segment_info_device(ctx, sources, n_sources, s.d_data, files_bytes, live, n_live, s.d_result, st);
+  if (rc) return rc;
+  if (hipMemcpyAsync(infos, s.d_result, need_i, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
+  return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *files,
+                                   uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size,
+                                   uint32_t flags, void *out, uint64_t out_bytes, rgb_seg_compact_result *result) {
+  if (!ctx || !out || !result || (files_bytes && !files) || (flags & ~RGB_SEG_COMPACT_VERIFY)) return RGB_E_INVAL;
+  uint64_t bound = 0;
+  uint32_t max_count = 0;
+  int rc = rgb_segment_compact_bound(sources, n_sources, live, n_live, files_bytes, &bound, &max_count);
+  if (rc) return rc;
+  if (!seg::headers_ok(sources, n_sources, (const unsigned char *)files)) return RGB_E_INVAL;
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  const uint64_t room = out_bytes < bound ? out_bytes : bound;         /* the image never needs more than the bound */
+  if (seg::grow(&s.d_data, &s.cap_d, (size_t)files_bytes) || seg::grow(&s.d_out, &s.cap_out, (size_t)room + 16u) ||
+      seg::grow(&s.d_result, &s.cap_result, sizeof(rgb_seg_compact_result)))
+    return RGB_E_NOMEM;
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (files_bytes && hipMemcpyAsync(s.d_data, files, files_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  rc = rgb_segment_compact_device(ctx, sources, n_sources, s.d_data, files_bytes, live, n_live, max_size, flags, s.d_out,
+                                  room, s.d_result, st);
+  if (rc) return rc;
+  rgb_seg_compact_result res;
+  if (hipMemcpyAsync(&res, s.d_result, sizeof res, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  /* only the image's own bytes come back, and only a good image */
+  if (res.status == RGB_SEG_COMPACT_OK) {
+    if (hipMemcpyAsync(out, s.d_out, res.file_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  }
+  *result = res;
   return RGB_OK;
 }

@@ -1,7 +1,9 @@
 /*
  * rgb_segment_host.cpp -- the host-only half of the segment part of include/ra_gpu_wal.h: the file layout and the
- * index walk of a segment file (src/ra_log_segment.erl:1118-1138, 1197-1219).  No HIP here, so the file also builds
- * on its own under the sanitizers (tests/test_segment.py::test_segment_scan_under_sanitizers).
+ * index walk of a segment file (src/ra_log_segment.erl:1118-1138, 1197-1219), and the descriptor checks of a compaction
+ * group.  No HIP here, so the file also builds on its own under the sanitizers
+ * (tests/test_segment.py::test_segment_scan_under_sanitizers,
+ * tests/test_segment_compact.py::test_compact_descriptors_under_sanitizers).
  */
 #include <stdint.h>
 #include "../../include/ra_gpu_wal.h"
@@ -14,6 +16,67 @@ extern "C" uint64_t rgb_segment_layout(const rgb_seg_entry *entries, uint32_t n,
     pos += entries[i].data_len;                                   /* data_offset = DataOffset + Length, :277 */
   }
   return pos;
+}
+
+/* ---- compaction: the descriptors of a group, checked before anything is enqueued ------------------------
+ * Library-internal (rgb_segment.hip calls it; not in the header).  `with_live` = 0: the slices are not looked at
+ * (rgb_segment_info without a live list).  `limit_count`: the live indexes are counted -- asked[s] per source,
+ * rank[i] = the number of live indexes of the same source in front of pair i, *max_count their sum -- and more than
+ * 65535 of them is refused; without it the three outputs are not written. */
+extern "C" int rgb_seg_compact_check(const rgb_seg_source *sources, uint32_t n_sources, const uint64_t *live,
+                                     uint32_t n_live, uint64_t files_bytes, int with_live, int limit_count,
+                                     uint32_t *asked, uint32_t *rank, uint64_t *sum_bytes, uint32_t *max_count) {
+  if (n_sources > RGB_SEG_COMPACT_MAX_SOURCES || (n_sources && !sources) || (n_live && !live)) return RGB_E_INVAL;
+  uint64_t sum = 0, total = 0;
+  for (uint32_t s = 0; s < n_sources; ++s) {
+    const rgb_seg_source &src = sources[s];
+    if (src.offset > files_bytes || src.n_bytes > files_bytes - src.offset) return RGB_E_INVAL;
+    if (sum + src.n_bytes < sum) return RGB_E_INVAL;
+    sum += src.n_bytes;
+    if (!with_live) continue;
+    if (src.live_first > n_live || src.live_n > n_live - src.live_first) return RGB_E_INVAL;
+    uint64_t in_source = 0;
+    for (uint32_t k = 0; k < src.live_n; ++k) {
+      const uint32_t i = src.live_first + k;
+      const uint64_t first = live[2 * (uint64_t)i], last = live[2 * (uint64_t)i + 1];
+      if (first > last) return RGB_E_INVAL;
+      if (k) {
+        const uint64_t prev_last = live[2 * (uint64_t)i - 1];
+        if (first <= prev_last || first - prev_last < 2u) return RGB_E_INVAL;       /* ascending, not adjacent */
+      }
+      if (!limit_count) continue;
+      const uint64_t count = last - first;                                          /* + 1, below */
+      if (count >= 65535u || in_source + count + 1u > 65535u) return RGB_E_INVAL;
+      rank[i] = (uint32_t)in_source;
+      in_source += count + 1u;
+    }
+    if (limit_count) {
+      asked[s] = (uint32_t)in_source;
+      total += in_source;
+      if (total > 65535u) return RGB_E_INVAL;
+    }
+  }
+  if (sum_bytes) *sum_bytes = sum;
+  if (limit_count) *max_count = (uint32_t)total;
+  return RGB_OK;
+}
+
+extern "C" int rgb_segment_compact_bound(const rgb_seg_source *sources, uint32_t n_sources, const uint64_t *live,
+                                         uint32_t n_live, uint64_t files_bytes, uint64_t *bound_out,
+                                         uint32_t *max_count_out) {
+  if (!bound_out || !max_count_out) return RGB_E_INVAL;
+  uint32_t asked[RGB_SEG_COMPACT_MAX_SOURCES];
+  uint32_t *rank = n_live ? new uint32_t[n_live] : nullptr;
+  uint64_t sum = 0;
+  uint32_t max_count = 0;
+  const int rc = rgb_seg_compact_check(sources, n_sources, live, n_live, files_bytes, 1, 1, asked, rank, &sum, &max_count);
+  delete[] rank;
+  if (rc) return rc;
+  const uint64_t head = (uint64_t)RGB_SEG_HEADER_BYTES + (uint64_t)RGB_SEG_RECORD_BYTES * max_count;
+  if (sum + head < sum) return RGB_E_INVAL;
+  *bound_out = head + sum;
+  *max_count_out = max_count;
+  return RGB_OK;
 }
 
 namespace {

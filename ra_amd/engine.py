@@ -46,7 +46,9 @@ OPTIONAL_IN_OLD_BUILDS = {"rgb_synth_tick_stamped_device", "rgb_synth_stamps_res
 WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "rgb_wal_frame_device",
                "rgb_wal_frame", "rgb_wal_scan", "rgb_wal_validate",
                "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
-               "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate"]                            # include/ra_gpu_wal.h
+               "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate",
+               "rgb_segment_compact_bound", "rgb_segment_info_device", "rgb_segment_info", "rgb_segment_compact_device",
+               "rgb_segment_compact"]                                                                                 # include/ra_gpu_wal.h
 
 
 class RgbError(RuntimeError):
@@ -207,6 +209,11 @@ def lib():
     L.rgb_segment_build.argtypes = [vp, vp, u32, u32, vp, C.c_uint64, vp, C.c_uint64, u32]
     L.rgb_segment_scan.argtypes = [vp, C.c_uint64, vp, u32, u32p, u32p, u32p, u32p]
     L.rgb_segment_validate.argtypes = [vp, vp, C.c_uint64, vp, u32, u32p]
+    L.rgb_segment_compact_bound.argtypes = [vp, u32, vp, u32, C.c_uint64, u64p, u32p]
+    L.rgb_segment_info_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, vp, vp]
+    L.rgb_segment_info.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, vp]
+    L.rgb_segment_compact_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp, C.c_uint64, vp, vp]
+    L.rgb_segment_compact.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp, C.c_uint64, vp]
     if L.rgb_abi_version() != abi.ABI_VERSION and not (os.environ.get("RGB_LIB") and L.rgb_abi_version() == abi.ABI_VERSION - 1):
         raise RuntimeError("ABI version mismatch")     # (RGB_LIB=<the previous ABI's build>: A/B timing, tools/ only)
     for i, dt in enumerate(abi.STRUCT_DTYPES):
@@ -638,6 +645,60 @@ class RaGpuBatch:
                                                  C.byref(n_ok)), "rgb_segment_validate")
         return n_ok.value
 
+    # -- major compaction: info/2 and copy/3 of a group of segment files (include/ra_gpu_wal.h) --
+    def segment_info_device(self, sources: np.ndarray, d_files: int, files_bytes: int, live, d_infos: int,
+                            stream: int = 0):
+        """One abi.SEG_INFO_DTYPE row per source into d_infos (ra_log_segment:info/2, src/ra_log_segment.erl:736-790).
+        `sources` (abi.SEG_SOURCE_DTYPE) and `live` ((first, last) pairs of uint64, or None: every record counts into
+        live_size) are host arrays; enqueues and returns."""
+        sources, live, n_live = _compact_args(sources, live)
+        self._check(self._L.rgb_segment_info_device(self._h, sources.ctypes.data if len(sources) else None, len(sources),
+                                                    d_files or None, files_bytes,
+                                                    live.ctypes.data if live is not None else None, n_live,
+                                                    d_infos or None, stream or None), "rgb_segment_info_device")
+
+    def segment_info(self, sources: np.ndarray, files: np.ndarray, live=None) -> np.ndarray:
+        """Host-buffer form of segment_info_device: the rows as abi.SEG_INFO_DTYPE."""
+        sources, live, n_live = _compact_args(sources, live)
+        files = np.ascontiguousarray(files, dtype=np.uint8)
+        infos = np.zeros(len(sources), dtype=abi.SEG_INFO_DTYPE)
+        self._check(self._L.rgb_segment_info(self._h, sources.ctypes.data if len(sources) else None, len(sources),
+                                             files.ctypes.data if len(files) else None, len(files),
+                                             live.ctypes.data if live is not None else None, n_live,
+                                             infos.ctypes.data if len(sources) else None), "rgb_segment_info")
+        return infos
+
+    def segment_compact_device(self, sources: np.ndarray, d_files: int, files_bytes: int, live, d_out: int,
+                               out_bytes: int, d_result: int, max_size: int = abi.SEG_MAX_SIZE_B, flags: int = 0,
+                               stream: int = 0):
+        """The live entries of every source copied into one new segment image at d_out (ra_log_segment:copy/3 for a
+        compaction group, src/ra_log_segments.erl:741-835); *d_result = one abi.SEG_COMPACT_RESULT_DTYPE record.
+        `sources` and `live` are host arrays; enqueues and returns."""
+        sources, live, n_live = _compact_args(sources, live)
+        self._check(self._L.rgb_segment_compact_device(self._h, sources.ctypes.data if len(sources) else None,
+                                                       len(sources), d_files or None, files_bytes,
+                                                       live.ctypes.data if live is not None else None, n_live, max_size,
+                                                       flags, d_out or None, out_bytes, d_result or None,
+                                                       stream or None), "rgb_segment_compact_device")
+
+    def segment_compact(self, sources: np.ndarray, files: np.ndarray, live, max_size: int = abi.SEG_MAX_SIZE_B,
+                        flags: int = 0, out: np.ndarray | None = None):
+        """Host-buffer form: (result record, image).  The image is `out[:file_bytes]` when the status is
+        abi.SEG_COMPACT_OK and None otherwise; `out` (uint8) defaults to a buffer of segment_compact_bound's size and is
+        written only when the status is OK, and only its first file_bytes bytes."""
+        sources, live, n_live = _compact_args(sources, live)
+        files = np.ascontiguousarray(files, dtype=np.uint8)
+        if out is None:
+            out = np.zeros(segment_compact_bound(sources, live, len(files))[0], dtype=np.uint8)
+        res = np.zeros(1, dtype=abi.SEG_COMPACT_RESULT_DTYPE)
+        self._check(self._L.rgb_segment_compact(self._h, sources.ctypes.data if len(sources) else None, len(sources),
+                                                files.ctypes.data if len(files) else None, len(files),
+                                                live.ctypes.data if live is not None else None, n_live, max_size, flags,
+                                                out.ctypes.data if len(out) else None, len(out), res.ctypes.data),
+                    "rgb_segment_compact")
+        ok = int(res["status"][0]) == abi.SEG_COMPACT_OK
+        return res[0], (out[:int(res["file_bytes"][0])] if ok else None)
+
     # -- observability -----------------------------------------------------------------
     def snapshot(self) -> np.ndarray:
         rows = np.zeros(self.n_groups, dtype=abi.LEADERBOARD_DTYPE)
@@ -797,6 +858,31 @@ def segment_layout(entries: np.ndarray, max_count: int = 4096):
     size = lib().rgb_segment_layout(entries.ctypes.data if len(entries) else None, len(entries), max_count,
                                     offs.ctypes.data if len(entries) else None)
     return offs, int(size)
+
+
+def _compact_args(sources, live):
+    """(sources as abi.SEG_SOURCE_DTYPE, the live list as a flat uint64 array or None, its number of pairs)"""
+    sources = np.ascontiguousarray(sources, dtype=abi.SEG_SOURCE_DTYPE)
+    if live is None:
+        return sources, None, 0
+    live = np.ascontiguousarray(live, dtype=np.uint64).reshape(-1)
+    if len(live) % 2:
+        raise ValueError("the live list is (first, last) pairs")
+    # an empty list is still a list ("nothing is live"), so it keeps a pointer
+    return sources, (live if len(live) else np.zeros(2, dtype=np.uint64)), len(live) // 2
+
+
+def segment_compact_bound(sources, live, files_bytes: int):
+    """(a size that always holds the compacted image, MaxCount = the number of live indexes) -- host helper, no
+    device work; RgbError(RGB_E_INVAL) for malformed descriptors, as the compact calls answer them."""
+    sources, live, n_live = _compact_args(sources, live)
+    bound, max_count = C.c_uint64(0), C.c_uint32(0)
+    rc = lib().rgb_segment_compact_bound(sources.ctypes.data if len(sources) else None, len(sources),
+                                         live.ctypes.data if live is not None else None, n_live, files_bytes,
+                                         C.byref(bound), C.byref(max_count))
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_compact_bound")
+    return int(bound.value), int(max_count.value)
 
 
 def segment_scan(file_bytes, cap: int | None = None):
