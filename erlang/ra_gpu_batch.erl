@@ -20,6 +20,7 @@
 -export([wal_batch_checksums/2, wal_frame/4, wal_recover_check/2, wal_frame_batch/3, wal_recover/2]).
 -export([crc32s/3, crc32_stream/3, segment_build/5, segment_image/4]).
 -export([segment_info/4, segment_compact/6, segment_compact_group/4]).
+-export([segment_flush/7, segment_flush_batch/5]).
 -export([encode_msg/3, encode_msgs/1, decode_decision/1, decision_to_effects/3]).
 
 -include_lib("ra/src/ra.hrl").
@@ -179,6 +180,61 @@ segment_compact_group(Ctx, Group, MaxSize, Verify) ->
                     end, {<<>>, [], <<>>, 0, 0}, Group),
     Flags = case Verify of true -> 1; false -> 0 end,
     segment_compact(Ctx, SourcesBin, iolist_to_binary(Files), LiveBin, MaxSize, Flags).
+
+%% mem-table flush (src/ra_log_segment_writer.erl:268-329, 425-500): the entries of every writer of a rolled-over WAL
+%% appended to the writers' segment files in one call.  WritersBin = one 48-byte record per writer, little endian:
+%% entry_first:32, entry_n:32 (its entries inside EntriesBin), open_count:32, open_max_count:32, open_data_bytes:64,
+%% range_first:64, range_last:64 (16#FFFFFFFFFFFFFFFF twice for `undefined`), 0:64.  EntriesBin as for crc32s.
+%% PiecesBin = one 80-byte record per run of entries in one file, sorted by writer and file: writer:32, ordinal:32,
+%% entry_first:32, entry_n:32, index_file_off:64, data_file_off:64, out_index_off:64, out_data_off:64, data_bytes:64,
+%% range_first:64, range_last:64, max_count:32, 0:32.
+segment_flush(_Ctx, _WritersBin, _EntriesBin, _DataBin, _MaxCount, _MaxSize, _Flags) -> erlang:nif_error(not_loaded).
+
+%% Writers = [{OpenState, [{Idx, Term, Bin}]}], OpenState = {Count, MaxCount, DataBytes, Range} of the writer's open
+%% segment (Count = (index_offset - 8) div 32, DataBytes = data_offset - data_start, Range = ra_log_segment:range/1:
+%% `undefined` or {First, Last}), the entries in append order.  -> {ok, PerWriter}: per writer, in file order,
+%% [{Ordinal, IndexFileOff, IndexIoData, DataFileOff, DataBin, Range}]: Ordinal 0 is the open segment, K its K-th
+%% successor (zpad_filename_incr K times, opened with MaxCount); IndexIoData goes to IndexFileOff -- for a successor
+%% it starts with the file header, at offset 0 -- and DataBin to DataFileOff; Range is the file's range afterwards.
+%% Opening and naming files, file:pwrite, sync, the ra_seq selection of what to flush and the `segments` notification
+%% stay in ra_log_segment_writer; an open segment of version 1 is finished through ra_log_segment itself.
+segment_flush_batch(Ctx, Writers, MaxCount, MaxSize, ComputeChecksums) ->
+    Undef = 16#FFFFFFFFFFFFFFFF,
+    {WritersBin, EntriesBin, Data, _, _} =
+        lists:foldl(fun({{Count, OpenMax, DataBytes, Range}, Entries}, {W, E0, D0, First, Off0}) ->
+                            {RF, RL} = case Range of undefined -> {Undef, Undef}; _ -> Range end,
+                            {E1, D1, Off1} =
+                                lists:foldl(fun({Idx, Term, Bin}, {E, D, Off}) ->
+                                                    Len = byte_size(Bin),
+                                                    {<<E/binary, Idx:64/little, Term:64/little, Off:64/little,
+                                                       Len:32/little, 0:32>>, [D, Bin], Off + Len}
+                                            end, {E0, D0, Off0}, Entries),
+                            N = length(Entries),
+                            {<<W/binary, First:32/little, N:32/little, Count:32/little, OpenMax:32/little,
+                               DataBytes:64/little, RF:64/little, RL:64/little, 0:64>>, E1, D1, First + N, Off1}
+                    end, {<<>>, <<>>, [], 0, 0}, Writers),
+    Flags = case ComputeChecksums of true -> 0; false -> 1 end,
+    case segment_flush(Ctx, WritersBin, EntriesBin, iolist_to_binary(Data), MaxCount, MaxSize, Flags) of
+        {ok, PiecesBin, Out} ->
+            Pieces = [{W, Ord, N, IFO, DFO, OIO, ODO, DB, {RF, RL}} ||
+                         <<W:32/little, Ord:32/little, _EF:32/little, N:32/little, IFO:64/little, DFO:64/little,
+                           OIO:64/little, ODO:64/little, DB:64/little, RF:64/little, RL:64/little, _MC:32/little,
+                           _:32>> <= PiecesBin],
+            Out1 = fun({_W, 0, N, IFO, DFO, OIO, ODO, DB, R}) ->
+                           {0, IFO, binary:part(Out, OIO, 32 * N), DFO, binary:part(Out, ODO, DB), R};
+                      ({_W, Ord, N, _IFO, DFO, OIO, ODO, DB, R}) ->
+                           {Ord, 0, binary:part(Out, OIO - 8, 8 + 32 * N), DFO, binary:part(Out, ODO, DB), R}
+                   end,
+            {ok, flush_pieces_by_writer(Pieces, 0, length(Writers), Out1)};
+        Error ->
+            Error
+    end.
+
+%% the pieces are sorted by writer: one pass
+flush_pieces_by_writer(_Pieces, WNo, NWriters, _Out1) when WNo >= NWriters -> [];
+flush_pieces_by_writer(Pieces, WNo, NWriters, Out1) ->
+    {Mine, Rest} = lists:splitwith(fun(P) -> element(1, P) =:= WNo end, Pieces),
+    [[Out1(P) || P <- Mine] | flush_pieces_by_writer(Rest, WNo + 1, NWriters, Out1)].
 
 %% The bytes of a whole segment file for Entries = [{Idx, Term, Bin}] in the caller's order: what
 %% ra_log_segment:append/4 accumulates in pending_index / pending_data and flush/1 writes

@@ -335,6 +335,94 @@ int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_
                         uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size, uint32_t flags,
                         void *out, uint64_t out_bytes, rgb_seg_compact_result *result);
 
+/* ==== mem-table flush: the entries of many writers appended to their segment files in one call ==========
+ *
+ * When a WAL file rolls over, ra_log_segment_writer flushes the mem tables of every writer that had entries in it
+ * (flush_mem_table_ranges/2, src/ra_log_segment_writer.erl:268-329): per writer the entries are appended to the
+ * writer's open segment, and a successor is opened whenever append/4 answers {error, full} (append_to_segment/6,
+ * :425-500; ra_log_segment:append/4 and is_full/1, src/ra_log_segment.erl:252-292, 1250-1255; flush/1, :316-338).
+ * One call here does that for W writers: it splits each writer's entries over its open segment and successors by the
+ * reference's rule, computes the CRCs while it copies the payloads and returns the exact bytes the host has to
+ * pwrite, with a table that says where each run of bytes goes.
+ *
+ * The rule.  Per writer, in entry order, the state is (count c, data bytes b, file k), at first (open_count,
+ * open_data_bytes, 0).  Before each entry the file is full iff c >= MaxCount of this file or b > max_size (strictly
+ * greater, and tested BEFORE the append: a file may exceed max_size by one entry, and a fresh file always takes at
+ * least one entry).  A full file is left: k += 1, c = 0, b = 0, MaxCount = the call's max_count.  The entry then gets
+ * DataOffset = 8 + 32 * MaxCount + b and its record <<Idx:64, Term:64, DataOffset:64, Length:32, Crc:32>> at
+ * 8 + 32 * c; then c += 1, b += Length.  The range of a file becomes {min(First, Idx), Idx} (update_range/2,
+ * :919-922): the LAST index wins even when it is lower.  An open segment that is already full yields no piece of
+ * ordinal 0: the writer's first piece then has ordinal 1.
+ *
+ * A piece is one run of appended entries in ONE file: two pwrites (index records, payloads).  Pieces are stored sorted
+ * by (writer, ordinal); `out` is packed in that order without padding: the 8 header bytes (ordinal > 0 only), the index
+ * records, the payloads.
+ *
+ * File I/O, fsync, file naming (zpad_filename_incr), maybe_open_new_segment, the ra_seq:floor / in_range / limit
+ * selection of which indexes to flush, term_to_iovec and the `segments` notification stay with the caller.  Only
+ * version-2 open segments are served: a writer whose open file is version 1 finishes that file through the reference
+ * path.  The sums open_data_bytes + payload bytes are the caller's to keep below 2^64.
+ *
+ * `writers` is a HOST array in every form: validated on the host, staged by the library.  RGB_E_INVAL, nothing
+ * enqueued: a slice outside n_entries, slices not ascending by entry_first or not disjoint, open_max_count or
+ * max_count outside 1 .. 65535, open_count > open_max_count, a range that is not (undefined iff open_count == 0,
+ * otherwise range_first <= range_last), unknown flags.  Entries that no slice names are ignored. */
+typedef struct rgb_seg_writer {      /* 48 bytes */
+  uint32_t entry_first, entry_n;     /* this writer's entries = entries[entry_first .. +entry_n), in append order */
+  uint32_t open_count;               /* index records already in its open segment: (index_offset - 8) / 32 */
+  uint32_t open_max_count;           /* MaxCount of the OPEN segment's header (successors take the call's max_count) */
+  uint64_t open_data_bytes;          /* data_offset - data_start of the open segment */
+  uint64_t range_first, range_last;  /* ra_log_segment:range/1 of the open segment; both RGB_UNDEF iff open_count == 0 */
+  uint64_t _pad;
+} rgb_seg_writer;
+
+typedef struct rgb_seg_piece {       /* 80 bytes: one run of appended entries in ONE file */
+  uint32_t writer, ordinal;          /* ordinal 0 = the open segment, k = its k-th successor */
+  uint32_t entry_first, entry_n;     /* global entry numbers; entry_n >= 1 always */
+  uint64_t index_file_off;           /* pwrite target of the index bytes: 8 + 32 * records already in the file */
+  uint64_t data_file_off;            /* pwrite target of the payload bytes */
+  uint64_t out_index_off;            /* out[out_index_off .. + 32 * entry_n) = the index records; when ordinal > 0 the 8
+                                        bytes in front of it are the header <<"RASG", 2:16, MaxCount:16>> */
+  uint64_t out_data_off, data_bytes; /* out[out_data_off .. + data_bytes) = the payloads back to back */
+  uint64_t range_first, range_last;  /* the file's range after the piece */
+  uint32_t max_count, _pad;          /* of this file */
+} rgb_seg_piece;
+
+typedef struct rgb_seg_flush_result {
+  uint32_t status;        /* RGB_SEG_FLUSH_* */
+  uint32_t n_pieces;      /* OK: rows written; SPACE: rows needed */
+  uint64_t out_bytes;     /* OK: bytes of `out` written; SPACE: bytes needed */
+  uint32_t writer, entry; /* ENTRY: the entry the status is about and its writer */
+  uint64_t _pad;
+} rgb_seg_flush_result;
+
+#define RGB_SEG_FLUSH_OK    0u
+#define RGB_SEG_FLUSH_SPACE 1u   /* out_bytes or pieces_cap too small; n_pieces and out_bytes say what is needed */
+#define RGB_SEG_FLUSH_ENTRY 2u   /* device form: the first entry, in entry order, whose payload lies outside d_data
+                                    (looked at before SPACE) */
+
+/* Host helper, pure: the descriptor validation of the calls below, and sizes that always suffice:
+ * *pieces_bound = n_entries (a piece holds at least one entry), *out_bound = data_bytes + 32 * n_entries +
+ * 8 * n_entries. */
+int rgb_segment_flush_bound(const rgb_seg_writer *writers, uint32_t n_writers, uint32_t n_entries, uint64_t data_bytes,
+                            uint64_t *out_bound, uint32_t *pieces_bound);
+
+/* d_entries: n_entries rgb_seg_entry rows in device memory (crc ignored), d_pieces: room for pieces_cap rgb_seg_piece
+ * rows (8-byte aligned), *d_result: one rgb_seg_flush_result; d_data and d_out may have any alignment.  d_pieces and
+ * d_out are written only when the status is OK, and then only their first n_pieces rows / out_bytes bytes.  flags:
+ * RGB_SEG_NO_CHECKSUMS.  Three launches on `stream` (NULL = the context's stream), no synchronisation.  The plan
+ * scratch lives in the context (released by rgb_close): one flush call per context at a time. */
+int rgb_segment_flush_device(rgb_ctx *ctx, const rgb_seg_writer *writers, uint32_t n_writers, const void *d_entries,
+                             uint32_t n_entries, const void *d_data, uint64_t data_bytes, uint32_t max_count,
+                             uint64_t max_size, uint32_t flags, void *d_pieces, uint32_t pieces_cap, void *d_out,
+                             uint64_t out_bytes, void *d_result, void *stream);
+/* Host-buffer form: synchronises; a payload outside `data` is RGB_E_INVAL; `pieces` and `out` are written only when
+ * the status is OK. */
+int rgb_segment_flush(rgb_ctx *ctx, const rgb_seg_writer *writers, uint32_t n_writers, const rgb_seg_entry *entries,
+                      uint32_t n_entries, const void *data, uint64_t data_bytes, uint32_t max_count, uint64_t max_size,
+                      uint32_t flags, rgb_seg_piece *pieces, uint32_t pieces_cap, void *out, uint64_t out_bytes,
+                      rgb_seg_flush_result *result);
+
 #ifdef __cplusplus
 }
 #endif

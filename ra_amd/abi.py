@@ -176,6 +176,17 @@ assert (SEG_SOURCE_DTYPE.itemsize, SEG_INFO_DTYPE.itemsize, SEG_COMPACT_RESULT_D
  SEG_COMPACT_BAD_SOURCE) = range(7)
 SEG_COMPACT_VERIFY = 1
 SEG_COMPACT_MAX_SOURCES = 256
+# mem-table flush (same header): one writer of a call, one run of appended entries in one file, the result
+SEG_WRITER_DTYPE = np.dtype([("entry_first", u32), ("entry_n", u32), ("open_count", u32), ("open_max_count", u32),
+                             ("open_data_bytes", u64), ("range_first", u64), ("range_last", u64), ("_pad", u64)])
+SEG_PIECE_DTYPE = np.dtype([("writer", u32), ("ordinal", u32), ("entry_first", u32), ("entry_n", u32),
+                            ("index_file_off", u64), ("data_file_off", u64), ("out_index_off", u64),
+                            ("out_data_off", u64), ("data_bytes", u64), ("range_first", u64), ("range_last", u64),
+                            ("max_count", u32), ("_pad", u32)])
+SEG_FLUSH_RESULT_DTYPE = np.dtype([("status", u32), ("n_pieces", u32), ("out_bytes", u64), ("writer", u32),
+                                   ("entry", u32), ("_pad", u64)])
+assert (SEG_WRITER_DTYPE.itemsize, SEG_PIECE_DTYPE.itemsize, SEG_FLUSH_RESULT_DTYPE.itemsize) == (48, 80, 32)
+SEG_FLUSH_OK, SEG_FLUSH_SPACE, SEG_FLUSH_ENTRY = range(3)
 
 # rgb_view (ABI v9, rgb_collect_view): pointers into the pinned slot the device wrote
 VIEW_DTYPE = np.dtype([("decisions", "<u8"), ("rpcs", "<u8"), ("tick", "<u8"), ("n", "<u4"), ("n_rpcs", "<u4"),

@@ -795,6 +795,39 @@ static ERL_NIF_TERM nif_segment_compact(ErlNifEnv *env, int argc, const ERL_NIF_
   return enif_make_tuple2(env, enif_make_atom(env, "error"), why);
 }
 
+/* segment_flush(Ctx, WritersBin, EntriesBin, DataBin, MaxCount, MaxSize, Flags) -> {ok, PiecesBin, OutBin} |
+ * {error, _}: the mem-table flush of every writer of a WAL file in one call (flush_mem_table_ranges/2 and
+ * append_to_segment/6, src/ra_log_segment_writer.erl:268-329, 425-500; ra_log_segment:append/4, is_full/1 and flush/1,
+ * src/ra_log_segment.erl:252-338, 1250-1255).  WritersBin = W rgb_seg_writer records, EntriesBin = n rgb_seg_entry
+ * records, DataBin = the packed payload bytes; PiecesBin = rgb_seg_piece records sorted by (writer, ordinal), OutBin
+ * = the bytes to pwrite, where the pieces say.  Flags: 1 = compute_checksums false. */
+static ERL_NIF_TERM nif_segment_flush(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary w, e, d, pieces, out; unsigned max_count, flags; uint64_t max_size, bound = 0; uint32_t rows = 0;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &w) || !enif_inspect_binary(env, argv[2], &e) ||
+      !enif_inspect_binary(env, argv[3], &d) || !enif_get_uint(env, argv[4], &max_count) ||
+      !enif_get_uint64(env, argv[5], &max_size) || !enif_get_uint(env, argv[6], &flags) ||
+      w.size % sizeof(rgb_seg_writer) != 0 || e.size % sizeof(rgb_seg_entry) != 0 ||
+      w.size / sizeof(rgb_seg_writer) > 0xFFFFFFFFu || e.size / sizeof(rgb_seg_entry) > 0xFFFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n_w = (uint32_t)(w.size / sizeof(rgb_seg_writer)), n = (uint32_t)(e.size / sizeof(rgb_seg_entry));
+  const rgb_seg_writer *writers = (const rgb_seg_writer *)w.data;
+  int rc = rgb_segment_flush_bound(writers, n_w, n, d.size, &bound, &rows);
+  if (rc) return mk_error(env, c, rc);
+  if (!enif_alloc_binary((size_t)(rows ? rows : 1) * sizeof(rgb_seg_piece), &pieces)) return mk_error(env, c, RGB_E_NOMEM);
+  if (!enif_alloc_binary((size_t)(bound ? bound : 1), &out)) { enif_release_binary(&pieces); return mk_error(env, c, RGB_E_NOMEM); }
+  rgb_seg_flush_result res;
+  rc = rgb_segment_flush(c->ctx, writers, n_w, (const rgb_seg_entry *)e.data, n, d.data, d.size, max_count, max_size,
+                         flags, (rgb_seg_piece *)pieces.data, rows, out.data, bound, &res);
+  if (rc || res.status != RGB_SEG_FLUSH_OK) {           /* (the bounds always suffice: no SPACE from here) */
+    enif_release_binary(&pieces); enif_release_binary(&out);
+    return mk_error(env, c, rc ? rc : RGB_E_INVAL);
+  }
+  enif_realloc_binary(&pieces, (size_t)res.n_pieces * sizeof(rgb_seg_piece));
+  enif_realloc_binary(&out, (size_t)res.out_bytes);
+  return enif_make_tuple3(env, enif_make_atom(env, "ok"), enif_make_binary(env, &pieces), enif_make_binary(env, &out));
+}
+
 static ErlNifFunc nif_funcs[] = {
   {"open", 4, nif_open, 0},
   {"register_groups", 3, nif_register_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
@@ -823,6 +856,7 @@ static ErlNifFunc nif_funcs[] = {
   {"segment_build", 5, nif_segment_build, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_info", 4, nif_segment_info, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_compact", 6, nif_segment_compact, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_flush", 7, nif_segment_flush, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(ra_gpu_batch, nif_funcs, on_load, NULL, NULL, NULL)

@@ -656,6 +656,354 @@ __global__ void rgb_compact_finish_kernel(const plan_rec *__restrict__ plan, con
   __builtin_memcpy(result_v, &res, sizeof res);
 }
 
+/* ---- mem-table flush (include/ra_gpu_wal.h, "mem-table flush") ---------------------------------------------
+ * Three passes, each its own launch, so that no workgroup ever waits for another:
+ *   plan   S lanes per writer (8, 16 or a wavefront, by the longest writer of the call), THREADS / S writers per step of
+ *          a workgroup, every workgroup a contiguous run of writers.  A writer goes through in chunks of S entries: an
+ *          LDS prefix sum of the lengths, then the sub-group's first lane walks the SEGMENTS of the chunk -- the next
+ *          boundary is the count limit or, by binary search on the prefix sums, the first entry with more than max_size
+ *          bytes in front of it -- with the file's and the running piece's state carried from chunk to chunk.  Every
+ *          entry then finds its segment and leaves its plan record, the first lane of a segment the minimum index; a
+ *          piece that ends is stored at its first entry's number.  Per writer: pieces and bytes of `out`, relative to
+ *          the writer's own start; per workgroup: their sums, and the first entry whose payload lies outside the data.
+ *   place  the same grid: every workgroup adds up the sums of all (the status, the result row) and of its predecessors,
+ *          then scans its own writers -- each writer's first piece row and first byte of `out` -- and turns the plan
+ *          record of each of their entries into places in `out` and in the file; a piece's first entry leaves the piece
+ *          row and, for a successor file, the header.  Nothing unless the status is OK.
+ *   copy   GROUP lanes per entry: the payload into `out` with its CRC in the same read, the index record.  Nothing
+ *          unless the status is OK.
+ * The kernels' parameter types are the unit's own (see "major compaction" above). */
+constexpr int FL_CHUNK = 64;                    /* entries per step of a writer at the widest sub-group */
+constexpr u32 FL_GRID_CAP = 1024u;              /* workgroups of plan and place: the sums every one of them adds up */
+
+struct fl_writer { u32 entry_first, entry_n, open_count, open_max_count; u64 open_data_bytes, range_first, range_last, _pad; };
+struct fl_entry { u64 idx, term, off; u32 len, crc; };
+struct alignas(16) fl_row { u64 out_bytes, out_base; u32 n_pieces, piece_base, first_ord, _pad; };   /* per writer */
+struct alignas(16) fl_plan { u64 pre, rel_out; u32 start, ordinal, writer, _pad; };                 /* per entry */
+struct alignas(16) fl_place { u64 dst_off, file_off, rec_off; u32 writer, _pad; };              /* per entry, over its fl_plan */
+struct alignas(16) fl_piece { u64 data_bytes, range_first, range_last; u32 entry_n, _pad; };        /* at a piece's first entry */
+struct alignas(16) fl_total { u64 out_bytes, bad; u32 n_pieces, _pad[3]; };                         /* per workgroup of plan */
+struct fl_seg { u64 rel_out, pre_base; u32 p0, p1, ordinal, start, n_before, closes; };             /* LDS: a piece's part in a chunk */
+static_assert(sizeof(fl_writer) == sizeof(rgb_seg_writer) && sizeof(fl_entry) == sizeof(rgb_seg_entry), "");
+static_assert(sizeof(fl_row) == 32 && sizeof(fl_plan) == 32 && sizeof(fl_place) == 32 && sizeof(fl_piece) == 32 && sizeof(fl_total) == 32, "");
+
+__device__ __forceinline__ void atomic_min64(u64 *p, u64 v) {
+  u64 old = *p;
+  while (v < old) {
+    const u64 seen = atomicCAS(p, old, v);
+    if (seen == old) break;
+    old = seen;
+  }
+}
+/* bytes in front of entry j of a chunk, from the chunk's inclusive prefix sums */
+__device__ __forceinline__ u64 fl_pex(const u64 *pre, u32 j) { return j ? pre[j - 1u] : 0ull; }
+
+template <int S>
+__global__ __launch_bounds__(THREADS) void rgb_flush_plan_kernel(
+    const fl_writer *__restrict__ writers, u32 n_writers, u32 per_block, const fl_entry *__restrict__ entries,
+    u64 data_bytes, u32 max_count, u64 max_size, fl_row *__restrict__ rows, fl_plan *__restrict__ plan,
+    fl_piece *__restrict__ pieces, fl_total *__restrict__ totals) {
+  constexpr u32 SUBS = THREADS / S;
+  __shared__ u64 s_pre[THREADS];                        /* inclusive prefix sums of the lengths, per sub-group */
+  __shared__ u64 s_idx[THREADS];
+  __shared__ fl_seg s_seg[THREADS];                     /* at most S segments in a chunk of S entries */
+  __shared__ u32 s_nseg[SUBS], s_chunks[SUBS];
+  __shared__ u64 s_min[SUBS];                           /* the minimum index of a piece that goes on in the next chunk */
+  __shared__ u64 s_tot_bytes, s_bad;
+  __shared__ u32 s_tot_pieces;
+  const u32 tid = threadIdx.x, sub = tid / (u32)S, ln = tid % (u32)S;
+  const u32 wb = blockIdx.x * per_block;
+  const u32 we = n_writers - wb < per_block ? n_writers : wb + per_block;
+  const u64 *pre = s_pre + sub * S;
+  const u64 *idxs = s_idx + sub * S;
+  fl_seg *segs = s_seg + sub * S;
+  if (tid == 0u) { s_tot_bytes = 0ull; s_bad = NONE64; s_tot_pieces = 0u; }
+  __syncthreads();
+  for (u32 r0 = wb; r0 < we; r0 += SUBS) {              /* the same for every lane */
+    const u32 w = r0 + sub;
+    const bool have = w < we;
+    fl_writer wd{};
+    if (have) wd = writers[w];
+    const u32 my_chunks = wd.entry_n / (u32)S + (wd.entry_n % (u32)S ? 1u : 0u);
+    if (ln == 0u) {
+      s_chunks[sub] = my_chunks;
+      if (have && !wd.entry_n) { fl_row z{}; rows[w] = z; }
+    }
+    __syncthreads();
+    u32 iters = 0;
+    for (u32 i = 0; i < SUBS; ++i) iters = s_chunks[i] > iters ? s_chunks[i] : iters;
+    __syncthreads();                                    /* (a step without entries has no other barrier before the next) */
+    /* the sub-group's first lane: the file (c, b, k, maxc), the running piece (pn entries, pb bytes, from entry pstart,
+     * at prel of the writer's part of `out`), the writer (rel bytes of `out`, npieces) */
+    u32 c = wd.open_count, maxc = wd.open_max_count, k = 0, pn = 0, pstart = 0, npieces = 0, first_ord = 0;
+    u64 b = wd.open_data_bytes, pb = 0, prel = 0, rel = 0, carry_min = NONE64, carry_last = 0;
+    for (u32 ch = 0; ch < iters; ++ch) {
+      const bool active = ch < my_chunks;
+      const u32 cbase = ch * (u32)S;
+      const u32 n_c = !active ? 0u : (wd.entry_n - cbase < (u32)S ? wd.entry_n - cbase : (u32)S);
+      const u32 e = wd.entry_first + cbase + ln;
+      const bool valid = ln < n_c;
+      fl_entry en{};
+      if (valid) {
+        en = entries[e];
+        if (en.off > data_bytes || en.len > data_bytes - en.off) atomic_min64(&s_bad, ((u64)e << 32) | w);
+      }
+      s_pre[tid] = valid ? (u64)en.len : 0ull;
+      s_idx[tid] = en.idx;
+      __syncthreads();
+      for (u32 off = 1; off < (u32)S; off <<= 1) {
+        u64 t = s_pre[tid];
+        if (ln >= off) t += s_pre[tid - off];
+        __syncthreads();
+        s_pre[tid] = t;
+        __syncthreads();
+      }
+      if (ln == 0u) {
+        u32 m = 0;
+        if (active) {
+          const bool last_chunk = ch + 1u == my_chunks;
+          if (pn) carry_min = s_min[sub];
+          u32 pos = 0;
+          while (pos < n_c) {
+            u32 bound = pos;
+            if (c < maxc && b <= max_size) {            /* not full: entry pos goes in, and its successors up to ... */
+              const u32 room = maxc - c;
+              const u32 j1 = n_c - pos < room ? n_c : pos + room;           /* ... the count limit, or */
+              const u64 lim = max_size - b, base = fl_pex(pre, pos);
+              u32 lo = pos + 1u, hi = j1;               /* ... the first with more than max_size bytes in front of it */
+              while (lo < hi) {
+                const u32 mid = (lo + hi) >> 1;
+                if (fl_pex(pre, mid) - base > lim) hi = mid; else lo = mid + 1u;
+              }
+              bound = lo;
+            }
+            if (bound > pos) {
+              if (!pn) {
+                pstart = wd.entry_first + cbase + pos; prel = rel;
+                if (k) rel += RGB_SEG_HEADER_BYTES;
+                if (!npieces) first_ord = k;
+                npieces += 1u;
+              }
+              const u64 bytes = fl_pex(pre, bound) - fl_pex(pre, pos);
+              fl_seg sg;
+              sg.rel_out = prel; sg.pre_base = pb; sg.p0 = pos; sg.p1 = bound; sg.ordinal = k; sg.start = pstart;
+              sg.n_before = pn; sg.closes = (bound < n_c || last_chunk) ? 1u : 0u;
+              segs[m++] = sg;
+              pn += bound - pos; pb += bytes; c += bound - pos; b += bytes;
+              rel += (u64)RGB_SEG_RECORD_BYTES * (bound - pos) + bytes;
+              if (sg.closes) { pn = 0u; pb = 0ull; }
+              if (bound < n_c) { k += 1u; c = 0u; b = 0ull; maxc = max_count; }
+              pos = bound;
+            } else {                                    /* full before entry pos (only the chunk's first can be) */
+              if (pn) {                                 /* the piece of the chunks before ends here */
+                fl_piece pc;
+                pc.data_bytes = pb; pc.entry_n = pn; pc._pad = 0u; pc.range_last = carry_last;
+                pc.range_first = (k == 0u && wd.open_count && wd.range_first < carry_min) ? wd.range_first : carry_min;
+                pieces[pstart] = pc;
+                pn = 0u; pb = 0ull;
+              }
+              k += 1u; c = 0u; b = 0ull; maxc = max_count;
+            }
+          }
+          carry_last = idxs[n_c - 1u];
+          if (last_chunk) {
+            fl_row r{};
+            r.out_bytes = rel; r.n_pieces = npieces; r.first_ord = first_ord;
+            rows[w] = r;
+            atomicAdd(&s_tot_bytes, rel);
+            atomicAdd(&s_tot_pieces, npieces);
+          }
+        }
+        s_nseg[sub] = m;
+      }
+      __syncthreads();
+      if (valid) {
+        u32 lo = 0, hi = s_nseg[sub];                   /* lo = segments that start at or in front of this entry */
+        while (lo < hi) {
+          const u32 mid = (lo + hi) >> 1;
+          if (segs[mid].p0 <= ln) lo = mid + 1u; else hi = mid;
+        }
+        const fl_seg sg = segs[lo - 1u];
+        fl_plan p;
+        p.pre = sg.pre_base + fl_pex(pre, ln) - fl_pex(pre, sg.p0);
+        p.rel_out = sg.rel_out; p.start = sg.start; p.ordinal = sg.ordinal; p.writer = w; p._pad = 0u;
+        plan[e] = p;
+        if (ln == sg.p0) {
+          u64 mn = NONE64;
+          for (u32 j = sg.p0; j < sg.p1; ++j) mn = idxs[j] < mn ? idxs[j] : mn;
+          if (sg.n_before && carry_min < mn) mn = carry_min;              /* (the sub-group's first lane) */
+          if (sg.closes) {
+            fl_piece pc;
+            pc.data_bytes = sg.pre_base + fl_pex(pre, sg.p1) - fl_pex(pre, sg.p0);
+            pc.entry_n = sg.n_before + sg.p1 - sg.p0; pc._pad = 0u;
+            pc.range_last = idxs[sg.p1 - 1u];
+            pc.range_first = (sg.ordinal == 0u && wd.open_count && wd.range_first < mn) ? wd.range_first : mn;
+            pieces[sg.start] = pc;
+          } else {
+            s_min[sub] = mn;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (tid == 0u) {
+    fl_total t{};
+    t.out_bytes = s_tot_bytes; t.bad = s_bad; t.n_pieces = s_tot_pieces;
+    totals[blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void rgb_flush_place_kernel(
+    const fl_writer *__restrict__ writers, u32 n_writers, u32 per_block, u32 n_blocks, const fl_total *__restrict__ totals,
+    fl_row *rows, fl_plan *plan, const fl_piece *__restrict__ pieces, u32 max_count, u32 pieces_cap, u64 out_bytes,
+    work_hdr *__restrict__ hdr, void *pieces_out_v, unsigned char *__restrict__ out, void *result_v) {
+  __shared__ u64 s_bytes[THREADS];
+  __shared__ u32 s_cnt[THREADS];
+  __shared__ u64 s_sum_bytes, s_base_bytes, s_bad;
+  __shared__ u32 s_sum_pieces, s_base_pieces;
+  const u32 tid = threadIdx.x;
+  if (tid == 0u) { s_sum_bytes = s_base_bytes = 0ull; s_bad = NONE64; s_sum_pieces = s_base_pieces = 0u; }
+  __syncthreads();
+  u64 sb = 0, bb = 0, bad = NONE64;
+  u32 sp = 0, bp = 0;
+  for (u32 i = tid; i < n_blocks; i += THREADS) {
+    const fl_total t = totals[i];
+    sb += t.out_bytes; sp += t.n_pieces;
+    if (i < blockIdx.x) { bb += t.out_bytes; bp += t.n_pieces; }
+    if (t.bad < bad) bad = t.bad;
+  }
+  if (sb) atomicAdd(&s_sum_bytes, sb);
+  if (bb) atomicAdd(&s_base_bytes, bb);
+  if (sp) atomicAdd(&s_sum_pieces, sp);
+  if (bp) atomicAdd(&s_base_pieces, bp);
+  if (bad != NONE64) atomic_min64(&s_bad, bad);
+  __syncthreads();
+  u32 status = RGB_SEG_FLUSH_OK;
+  if (s_bad != NONE64) status = RGB_SEG_FLUSH_ENTRY;
+  else if (s_sum_pieces > pieces_cap || s_sum_bytes > out_bytes) status = RGB_SEG_FLUSH_SPACE;
+  if (blockIdx.x == 0u && tid == 0u) {
+    rgb_seg_flush_result res{};
+    res.status = status;
+    if (status == RGB_SEG_FLUSH_ENTRY) { res.entry = (u32)(s_bad >> 32); res.writer = (u32)s_bad; }
+    else { res.n_pieces = s_sum_pieces; res.out_bytes = s_sum_bytes; }
+    hdr->status = status;
+    hdr->crc_fail = NONE32;
+    __builtin_memcpy(result_v, &res, sizeof res);
+  }
+  if (status != RGB_SEG_FLUSH_OK) return;               /* the same for every lane of every workgroup */
+  const u32 wb = blockIdx.x * per_block;
+  if (wb >= n_writers) return;
+  const u32 we = n_writers - wb < per_block ? n_writers : wb + per_block;
+  u64 run_bytes = s_base_bytes;
+  u32 run_cnt = s_base_pieces;
+  for (u32 base = wb; base < we; base += THREADS) {
+    const u32 w = base + tid;
+    const bool valid = w < we;
+    fl_row r{};
+    if (valid) r = rows[w];
+    s_bytes[tid] = r.out_bytes; s_cnt[tid] = r.n_pieces;
+    __syncthreads();
+    for (u32 off = 1; off < THREADS; off <<= 1) {
+      u64 tb = s_bytes[tid];
+      u32 tc = s_cnt[tid];
+      if (tid >= off) { tb += s_bytes[tid - off]; tc += s_cnt[tid - off]; }
+      __syncthreads();
+      s_bytes[tid] = tb; s_cnt[tid] = tc;
+      __syncthreads();
+    }
+    if (valid) {
+      r.out_base = run_bytes + s_bytes[tid] - r.out_bytes;
+      r.piece_base = run_cnt + s_cnt[tid] - r.n_pieces;
+      rows[w] = r;
+    }
+    run_bytes += s_bytes[THREADS - 1];
+    run_cnt += s_cnt[THREADS - 1];
+    __syncthreads();
+  }
+  /* the entries of this workgroup's writers (one run of the entry array: the slices ascend): where each one's record
+   * and payload go in `out`, what its record says; a piece's first entry also leaves the piece row and, for a
+   * successor file, the header */
+  const fl_writer w_last = writers[we - 1u];
+  const u32 e_end = w_last.entry_first + w_last.entry_n;
+  for (u32 e = writers[wb].entry_first + tid; e < e_end; e += THREADS) {
+    const fl_plan p = plan[e];
+    if (p.writer == NONE32) continue;                   /* an entry of no writer */
+    const fl_row r = rows[p.writer];
+    const fl_piece pc = pieces[p.start];
+    const bool open_file = p.ordinal == 0u;
+    u32 file_max = max_count, in_file = 0;
+    u64 open_bytes = 0;
+    if (open_file) {
+      const fl_writer wd = writers[p.writer];
+      file_max = wd.open_max_count; in_file = wd.open_count; open_bytes = wd.open_data_bytes;
+    }
+    const u64 piece_off = r.out_base + p.rel_out;                        /* positions in `out` ... */
+    const u64 index_off = piece_off + (open_file ? 0u : RGB_SEG_HEADER_BYTES);
+    const u64 data_off = index_off + (u64)RGB_SEG_RECORD_BYTES * pc.entry_n;
+    const u64 file_data = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * file_max + open_bytes;   /* ... and in the file */
+    fl_place d;
+    d.dst_off = data_off + p.pre; d.file_off = file_data + p.pre;
+    d.rec_off = index_off + (u64)RGB_SEG_RECORD_BYTES * (e - p.start);
+    d.writer = p.writer; d._pad = 0u;
+    *reinterpret_cast<fl_place *>(plan + e) = d;
+    if (e == p.start) {
+      if (!open_file) {                                 /* <<"RASG", 2:16, MaxCount:16>> */
+        struct __attribute__((packed)) hdr8 { u64 v; } h;
+        h.v = 0x47534152ull | (0x0200ull << 32) | ((u64)((max_count >> 8) & 0xFFu) << 48) | ((u64)(max_count & 0xFFu) << 56);
+        __builtin_memcpy(out + piece_off, &h, 8);
+      }
+      rgb_seg_piece row;
+      row.writer = p.writer; row.ordinal = p.ordinal; row.entry_first = e; row.entry_n = pc.entry_n;
+      row.index_file_off = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * in_file;
+      row.data_file_off = file_data;
+      row.out_index_off = index_off; row.out_data_off = data_off; row.data_bytes = pc.data_bytes;
+      row.range_first = pc.range_first; row.range_last = pc.range_last;
+      row.max_count = file_max; row._pad = 0u;
+      reinterpret_cast<rgb_seg_piece *>(pieces_out_v)[r.piece_base + (p.ordinal - r.first_ord)] = row;
+    }
+  }
+}
+
+template <int GROUP>
+__global__ __launch_bounds__(THREADS) void rgb_flush_copy_kernel(
+    const fl_entry *__restrict__ entries, u32 n, const unsigned char *__restrict__ data, const fl_place *__restrict__ placed,
+    const work_hdr *__restrict__ hdr, u32 flags, unsigned char *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) u32 lds[LDS_WORDS];
+  if (hdr->status != RGB_SEG_FLUSH_OK) return;          /* decided before this launch: the same for every lane */
+  load_tables<GROUP>(lds);
+  constexpr u32 PER_BLOCK = THREADS / GROUP;
+  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
+  const u32 lane = threadIdx.x & (GROUP - 1);
+  for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
+    const u32 e = base + threadIdx.x / GROUP;
+    bool live = e < n;
+    fl_place d{};
+    if (live) { d = placed[e]; live = d.writer != NONE32; }               /* an entry of no writer */
+    fl_entry en{};
+    if (live) en = entries[e];
+    const u32 len = en.len;
+    const unsigned char *pay = data + en.off;
+    unsigned char *dst = out + d.dst_off;
+    const bool wide = live && len >= 16u;
+    const u32 part = lane_raw<GROUP, UNROLL, true>(lds, pay, dst, wide ? len : 0u, lane, 0xFFFFFFFFu);
+    u32 crc = ~group_xor<GROUP>(part);
+    if (live && lane == 0u) {
+      if (!wide) crc = crc_bytes(lds, 0u, pay, len, dst);
+      if (flags & RGB_SEG_NO_CHECKSUMS) crc = 0u;
+      v4u a, b;
+      a.x = __builtin_bswap32((u32)(en.idx >> 32));     a.y = __builtin_bswap32((u32)en.idx);
+      a.z = __builtin_bswap32((u32)(en.term >> 32));    a.w = __builtin_bswap32((u32)en.term);
+      b.x = __builtin_bswap32((u32)(d.file_off >> 32)); b.y = __builtin_bswap32((u32)d.file_off);
+      b.z = __builtin_bswap32(len);                     b.w = __builtin_bswap32(crc);
+      unsigned char *rec = out + d.rec_off;
+      *reinterpret_cast<v4u_any *>(rec) = a;
+      *reinterpret_cast<v4u_any *>(rec + 16) = b;
+    }
+  }
+}
+
 /* x^(8 n) mod P on the host */
 inline u32 host_xpow8(u64 n) { return xpow8_c(n); }
 
@@ -685,6 +1033,12 @@ struct stage {
   size_t cap_hdesc = 0, cap_desc = 0, cap_work = 0, cap_result = 0;
   hipEvent_t staged = nullptr;
   bool staged_recorded = false;
+  /* mem-table flush: the writers of a call (pinned, and their device copy), the scratch plan, and for the host-buffer
+   * form the piece rows and the result; fl_staged as `staged` */
+  void *h_fl = nullptr, *d_fl = nullptr, *d_fl_work = nullptr, *d_fl_pieces = nullptr, *d_fl_result = nullptr;
+  size_t cap_hfl = 0, cap_fl = 0, cap_fl_work = 0, cap_fl_pieces = 0, cap_fl_result = 0;
+  hipEvent_t fl_staged = nullptr;
+  bool fl_recorded = false;
 };
 std::recursive_mutex g_mu;     /* the host-buffer forms call the device forms with it held */
 std::unordered_map<rgb_ctx *, stage> g_stages;
@@ -713,10 +1067,13 @@ extern "C" void rgb_seg_release(rgb_ctx *ctx) {      /* called by rgb_close */
   auto it = seg::g_stages.find(ctx);
   if (it == seg::g_stages.end()) return;
   seg::stage &s = it->second;
-  void *all[] = {s.d_entries, s.d_data, s.d_crcs, s.d_offsets, s.d_out, s.d_partials, s.d_desc, s.d_work, s.d_result};
+  void *all[] = {s.d_entries, s.d_data, s.d_crcs, s.d_offsets, s.d_out, s.d_partials, s.d_desc, s.d_work, s.d_result,
+                 s.d_fl, s.d_fl_work, s.d_fl_pieces, s.d_fl_result};
   for (void *p : all) if (p) (void)hipFree(p);
   if (s.h_desc) (void)hipHostFree(s.h_desc);
+  if (s.h_fl) (void)hipHostFree(s.h_fl);
   if (s.staged) (void)hipEventDestroy(s.staged);
+  if (s.fl_staged) (void)hipEventDestroy(s.fl_staged);
   seg::g_stages.erase(it);
 }
 
@@ -1093,6 +1450,153 @@ extern "C" int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, 
   /* only the image's own bytes come back, and only a good image */
   if (res.status == RGB_SEG_COMPACT_OK) {
     if (hipMemcpyAsync(out, s.d_out, res.file_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  }
+  *result = res;
+  return RGB_OK;
+}
+
+/* ---- mem-table flush: the entries of many writers into their segment files ------------------------------ */
+
+extern "C" int rgb_seg_flush_check(const rgb_seg_writer *writers, uint32_t n_writers, uint32_t n_entries,
+                                   uint32_t *covered, uint32_t *longest);
+
+extern "C" int rgb_segment_flush_device(rgb_ctx *ctx, const rgb_seg_writer *writers, uint32_t n_writers,
+                                        const void *d_entries, uint32_t n_entries, const void *d_data, uint64_t data_bytes,
+                                        uint32_t max_count, uint64_t max_size, uint32_t flags, void *d_pieces,
+                                        uint32_t pieces_cap, void *d_out, uint64_t out_bytes, void *d_result, void *stream) {
+  if (!ctx || !d_result || (n_writers && !writers) || (n_entries && !d_entries) || (data_bytes && !d_data) ||
+      (pieces_cap && !d_pieces) || (out_bytes && !d_out) || (flags & ~RGB_SEG_NO_CHECKSUMS))
+    return RGB_E_INVAL;
+  if (max_count < 1u || max_count > 65535u) return RGB_E_INVAL;
+  uint32_t covered = 0, longest = 0;
+  int rc = rgb_seg_flush_check(writers, n_writers, n_entries, &covered, &longest);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  /* the sub-group of the plan, by the longest writer; every workgroup a whole number of steps of it */
+  const seg::u32 width = longest <= 8u ? 8u : longest <= 16u ? 16u : (seg::u32)seg::FL_CHUNK;
+  const seg::u32 subs = seg::THREADS / width;
+  seg::u32 grid = (n_writers + subs - 1u) / subs;
+  if (grid > seg::FL_GRID_CAP) grid = seg::FL_GRID_CAP;
+  if (grid == 0u) grid = 1u;
+  seg::u32 per_block = (n_writers + grid - 1u) / grid;
+  per_block = (per_block + subs - 1u) / subs * subs;
+  if (per_block == 0u) per_block = subs;
+  const seg::u32 n_blocks = (n_writers + per_block - 1u) / per_block;      /* 0 without writers */
+  /* the writers, through the context's pinned buffer */
+  const size_t need = (size_t)n_writers * sizeof(seg::fl_writer) + 16u;
+  if (!s.fl_staged && hipEventCreateWithFlags(&s.fl_staged, hipEventDisableTiming) != hipSuccess) return RGB_E_HIP;
+  if (s.fl_recorded && hipEventSynchronize(s.fl_staged) != hipSuccess) return RGB_E_HIP;
+  s.fl_recorded = false;
+  if (need > s.cap_hfl) {
+    if (s.h_fl) (void)hipHostFree(s.h_fl);
+    s.h_fl = nullptr; s.cap_hfl = 0;
+    if (hipHostMalloc(&s.h_fl, need * 2u, hipHostMallocDefault) != hipSuccess) return RGB_E_NOMEM;
+    s.cap_hfl = need * 2u;
+  }
+  if (n_writers) memcpy(s.h_fl, writers, (size_t)n_writers * sizeof(seg::fl_writer));
+  /* the scratch: a row per writer, the sums of the plan's workgroups, the status, a plan record and a piece per entry */
+  const size_t off_tot = (size_t)n_writers * sizeof(seg::fl_row);
+  const size_t off_hdr = off_tot + (size_t)seg::FL_GRID_CAP * sizeof(seg::fl_total);
+  const size_t off_plan = off_hdr + sizeof(seg::work_hdr);
+  const size_t off_pieces = off_plan + (size_t)n_entries * sizeof(seg::fl_plan);
+  const size_t work = off_pieces + (size_t)n_entries * sizeof(seg::fl_piece) + 16u;
+  if (seg::grow(&s.d_fl, &s.cap_fl, need) || seg::grow(&s.d_fl_work, &s.cap_fl_work, work)) return RGB_E_NOMEM;
+  if (hipMemcpyAsync(s.d_fl, s.h_fl, need, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  if (hipEventRecord(s.fl_staged, st) != hipSuccess) return RGB_E_HIP;
+  s.fl_recorded = true;
+  unsigned char *w = (unsigned char *)s.d_fl_work;
+  const seg::fl_writer *d_writers = (const seg::fl_writer *)s.d_fl;
+  seg::fl_row *d_rows = (seg::fl_row *)w;
+  seg::fl_total *d_totals = (seg::fl_total *)(w + off_tot);
+  seg::work_hdr *d_hdr = (seg::work_hdr *)(w + off_hdr);
+  seg::fl_plan *d_plan = (seg::fl_plan *)(w + off_plan);
+  seg::fl_piece *d_pc = (seg::fl_piece *)(w + off_pieces);
+  /* entries that no writer names keep writer = NONE32 in their plan record: the copy passes them by */
+  if (covered != n_entries &&
+      hipMemsetAsync(d_plan, 0xFF, (size_t)n_entries * sizeof(seg::fl_plan), st) != hipSuccess)
+    return RGB_E_HIP;
+  (void)hipGetLastError();
+#define SEG_PLAN_LAUNCH(S)                                                                                           \
+  hipLaunchKernelGGL((seg::rgb_flush_plan_kernel<S>), dim3(n_blocks), dim3(seg::THREADS), 0, st, d_writers, n_writers,  \
+                     per_block, (const seg::fl_entry *)d_entries, (seg::u64)data_bytes, max_count, (seg::u64)max_size, \
+                     d_rows, d_plan, d_pc, d_totals)
+  if (n_blocks) {
+    if (width == 8u) SEG_PLAN_LAUNCH(8);
+    else if (width == 16u) SEG_PLAN_LAUNCH(16);
+    else SEG_PLAN_LAUNCH(64);
+  }
+#undef SEG_PLAN_LAUNCH
+  hipLaunchKernelGGL(seg::rgb_flush_place_kernel, dim3(n_blocks ? n_blocks : 1u), dim3(seg::THREADS), 0, st, d_writers,
+                     n_writers, per_block, n_blocks, (const seg::fl_total *)d_totals, d_rows, d_plan,
+                     (const seg::fl_piece *)d_pc, max_count, pieces_cap, (seg::u64)out_bytes, d_hdr, d_pieces,
+                     (unsigned char *)d_out, d_result);
+  if (n_entries && n_writers) {
+    /* the lane-group width of rgb_segment_build_device */
+    const uint32_t n = n_entries;
+    const uint64_t mean = data_bytes / n;
+#define SEG_FLUSH_LAUNCH(G)                                                                                          \
+  do {                                                                                                               \
+    const seg::u32 per = seg::THREADS / (G);                                                                         \
+    seg::u32 cgrid = (n + per - 1) / per;                                                                            \
+    if (cgrid > seg::GRID_CAP) cgrid = seg::GRID_CAP;                                                                \
+    hipLaunchKernelGGL((seg::rgb_flush_copy_kernel<G>), dim3(cgrid), dim3(seg::THREADS), 0, st,                      \
+                       (const seg::fl_entry *)d_entries, n, (const unsigned char *)d_data,                           \
+                       (const seg::fl_place *)d_plan, (const seg::work_hdr *)d_hdr, flags, (unsigned char *)d_out);  \
+  } while (0)
+    if (mean <= 320u) SEG_FLUSH_LAUNCH(8);
+    else if (mean < 1024u) SEG_FLUSH_LAUNCH(16);
+    else SEG_FLUSH_LAUNCH(64);
+#undef SEG_FLUSH_LAUNCH
+  }
+  return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_segment_flush(rgb_ctx *ctx, const rgb_seg_writer *writers, uint32_t n_writers,
+                                 const rgb_seg_entry *entries, uint32_t n_entries, const void *data, uint64_t data_bytes,
+                                 uint32_t max_count, uint64_t max_size, uint32_t flags, rgb_seg_piece *pieces,
+                                 uint32_t pieces_cap, void *out, uint64_t out_bytes, rgb_seg_flush_result *result) {
+  if (!ctx || !result || (n_entries && !entries) || (data_bytes && !data) || (pieces_cap && !pieces) ||
+      (out_bytes && !out) || (flags & ~RGB_SEG_NO_CHECKSUMS))
+    return RGB_E_INVAL;
+  if (max_count < 1u || max_count > 65535u) return RGB_E_INVAL;
+  uint64_t bound = 0;
+  uint32_t pieces_bound = 0;
+  int rc = rgb_segment_flush_bound(writers, n_writers, n_entries, data_bytes, &bound, &pieces_bound);
+  if (rc) return rc;
+  for (uint32_t w = 0; w < n_writers; ++w)
+    for (uint32_t i = 0; i < writers[w].entry_n; ++i) {
+      const rgb_seg_entry &e = entries[writers[w].entry_first + i];
+      if (!seg::slice_ok(e.data_offset, e.data_len, data_bytes)) return RGB_E_INVAL;
+    }
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  const uint64_t room = out_bytes < bound ? out_bytes : bound;             /* the call never needs more than the bounds */
+  const uint32_t rows = pieces_cap < pieces_bound ? pieces_cap : pieces_bound;
+  const size_t need_e = (size_t)n_entries * sizeof(rgb_seg_entry);
+  if (seg::grow(&s.d_entries, &s.cap_e, need_e) || seg::grow(&s.d_data, &s.cap_d, (size_t)data_bytes) ||
+      seg::grow(&s.d_out, &s.cap_out, (size_t)room + 16u) ||
+      seg::grow(&s.d_fl_pieces, &s.cap_fl_pieces, (size_t)rows * sizeof(rgb_seg_piece) + 16u) ||
+      seg::grow(&s.d_fl_result, &s.cap_fl_result, sizeof(rgb_seg_flush_result)))
+    return RGB_E_NOMEM;
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (n_entries && hipMemcpyAsync(s.d_entries, entries, need_e, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  if (data_bytes && hipMemcpyAsync(s.d_data, data, data_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  rc = rgb_segment_flush_device(ctx, writers, n_writers, s.d_entries, n_entries, s.d_data, data_bytes, max_count, max_size,
+                                flags, s.d_fl_pieces, rows, s.d_out, room, s.d_fl_result, st);
+  if (rc) return rc;
+  rgb_seg_flush_result res;
+  if (hipMemcpyAsync(&res, s.d_fl_result, sizeof res, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  /* only the rows and bytes of the answer come back, and only a good answer */
+  if (res.status == RGB_SEG_FLUSH_OK) {
+    if (res.n_pieces && hipMemcpyAsync(pieces, s.d_fl_pieces, (size_t)res.n_pieces * sizeof(rgb_seg_piece),
+                                       hipMemcpyDeviceToHost, st) != hipSuccess)
+      return RGB_E_HIP;
+    if (res.out_bytes && hipMemcpyAsync(out, s.d_out, res.out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
   }
   *result = res;

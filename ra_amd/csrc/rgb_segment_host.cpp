@@ -1,9 +1,10 @@
 /*
  * rgb_segment_host.cpp -- the host-only half of the segment part of include/ra_gpu_wal.h: the file layout and the
  * index walk of a segment file (src/ra_log_segment.erl:1118-1138, 1197-1219), and the descriptor checks of a compaction
- * group.  No HIP here, so the file also builds on its own under the sanitizers
+ * group and of a mem-table flush.  No HIP here, so the file also builds on its own under the sanitizers
  * (tests/test_segment.py::test_segment_scan_under_sanitizers,
- * tests/test_segment_compact.py::test_compact_descriptors_under_sanitizers).
+ * tests/test_segment_compact.py::test_compact_descriptors_under_sanitizers,
+ * tests/test_segment_flush.py::test_flush_descriptors_under_sanitizers).
  */
 #include <stdint.h>
 #include "../../include/ra_gpu_wal.h"
@@ -76,6 +77,45 @@ extern "C" int rgb_segment_compact_bound(const rgb_seg_source *sources, uint32_t
   if (sum + head < sum) return RGB_E_INVAL;
   *bound_out = head + sum;
   *max_count_out = max_count;
+  return RGB_OK;
+}
+
+/* ---- mem-table flush: the writers of a call, checked before anything is enqueued -------------------------
+ * Library-internal (rgb_segment.hip calls it; not in the header).  *covered = the entries the slices name,
+ * *longest = the longest slice. */
+extern "C" int rgb_seg_flush_check(const rgb_seg_writer *writers, uint32_t n_writers, uint32_t n_entries,
+                                   uint32_t *covered, uint32_t *longest) {
+  if (n_writers && !writers) return RGB_E_INVAL;
+  uint64_t next = 0, sum = 0;                                      /* the first entry a later slice may name */
+  uint32_t top = 0;
+  for (uint32_t w = 0; w < n_writers; ++w) {
+    const rgb_seg_writer &d = writers[w];
+    if (d.entry_first > n_entries || d.entry_n > n_entries - d.entry_first) return RGB_E_INVAL;
+    if (d.entry_first < next) return RGB_E_INVAL;                  /* ascending and disjoint */
+    next = (uint64_t)d.entry_first + d.entry_n;
+    if (d.open_max_count < 1u || d.open_max_count > 65535u || d.open_count > d.open_max_count) return RGB_E_INVAL;
+    if (d.open_count == 0u) {
+      if (d.range_first != RGB_UNDEF || d.range_last != RGB_UNDEF) return RGB_E_INVAL;
+    } else if (d.range_first == RGB_UNDEF || d.range_last == RGB_UNDEF || d.range_first > d.range_last) {
+      return RGB_E_INVAL;
+    }
+    sum += d.entry_n;
+    if (d.entry_n > top) top = d.entry_n;
+  }
+  if (covered) *covered = (uint32_t)sum;                           /* <= n_entries: the slices are disjoint */
+  if (longest) *longest = top;
+  return RGB_OK;
+}
+
+extern "C" int rgb_segment_flush_bound(const rgb_seg_writer *writers, uint32_t n_writers, uint32_t n_entries,
+                                       uint64_t data_bytes, uint64_t *out_bound, uint32_t *pieces_bound) {
+  if (!out_bound || !pieces_bound) return RGB_E_INVAL;
+  const int rc = rgb_seg_flush_check(writers, n_writers, n_entries, nullptr, nullptr);
+  if (rc) return rc;
+  const uint64_t per_entry = (uint64_t)(RGB_SEG_RECORD_BYTES + RGB_SEG_HEADER_BYTES) * n_entries;
+  if (data_bytes + per_entry < data_bytes) return RGB_E_INVAL;
+  *out_bound = data_bytes + per_entry;
+  *pieces_bound = n_entries;
   return RGB_OK;
 }
 

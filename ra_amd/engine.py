@@ -48,7 +48,7 @@ WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "r
                "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
                "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate",
                "rgb_segment_compact_bound", "rgb_segment_info_device", "rgb_segment_info", "rgb_segment_compact_device",
-               "rgb_segment_compact"]                                                                                 # include/ra_gpu_wal.h
+               "rgb_segment_compact", "rgb_segment_flush_bound", "rgb_segment_flush_device", "rgb_segment_flush"]                                                                                 # include/ra_gpu_wal.h
 
 
 class RgbError(RuntimeError):
@@ -214,6 +214,10 @@ def lib():
     L.rgb_segment_info.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, vp]
     L.rgb_segment_compact_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp, C.c_uint64, vp, vp]
     L.rgb_segment_compact.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp, C.c_uint64, vp]
+    L.rgb_segment_flush_bound.argtypes = [vp, u32, u32, C.c_uint64, u64p, u32p]
+    L.rgb_segment_flush_device.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp,
+                                           C.c_uint64, vp, vp]
+    L.rgb_segment_flush.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp, C.c_uint64, vp]
     if L.rgb_abi_version() != abi.ABI_VERSION and not (os.environ.get("RGB_LIB") and L.rgb_abi_version() == abi.ABI_VERSION - 1):
         raise RuntimeError("ABI version mismatch")     # (RGB_LIB=<the previous ABI's build>: A/B timing, tools/ only)
     for i, dt in enumerate(abi.STRUCT_DTYPES):
@@ -699,6 +703,46 @@ class RaGpuBatch:
         ok = int(res["status"][0]) == abi.SEG_COMPACT_OK
         return res[0], (out[:int(res["file_bytes"][0])] if ok else None)
 
+    # -- mem-table flush: the entries of many writers into their segment files (include/ra_gpu_wal.h) --
+    def segment_flush_device(self, writers: np.ndarray, d_entries: int, n_entries: int, d_data: int, data_bytes: int,
+                             d_pieces: int, pieces_cap: int, d_out: int, out_bytes: int, d_result: int,
+                             max_count: int = abi.SEG_MAX_ENTRIES, max_size: int = abi.SEG_MAX_SIZE_B, flags: int = 0,
+                             stream: int = 0):
+        """The entries of every writer split over its open segment and successors (ra_log_segment_writer's flush,
+        src/ra_log_segment_writer.erl:268-329, 425-500): abi.SEG_PIECE_DTYPE rows into d_pieces, the bytes to pwrite
+        into d_out, one abi.SEG_FLUSH_RESULT_DTYPE record into d_result.  `writers` (abi.SEG_WRITER_DTYPE) is a host
+        array; enqueues and returns."""
+        writers = np.ascontiguousarray(writers, dtype=abi.SEG_WRITER_DTYPE)
+        self._check(self._L.rgb_segment_flush_device(self._h, writers.ctypes.data if len(writers) else None, len(writers),
+                                                     d_entries or None, n_entries, d_data or None, data_bytes, max_count,
+                                                     max_size, flags, d_pieces or None, pieces_cap, d_out or None,
+                                                     out_bytes, d_result or None, stream or None),
+                    "rgb_segment_flush_device")
+
+    def segment_flush(self, writers: np.ndarray, entries: np.ndarray, data: np.ndarray,
+                      max_count: int = abi.SEG_MAX_ENTRIES, max_size: int = abi.SEG_MAX_SIZE_B, flags: int = 0,
+                      pieces: np.ndarray | None = None, out: np.ndarray | None = None):
+        """Host-buffer form: (result record, piece rows, out bytes).  Rows and bytes are `pieces[:n_pieces]` and
+        `out[:out_bytes]` when the status is abi.SEG_FLUSH_OK and None otherwise; both buffers default to
+        segment_flush_bound's sizes and are written only when the status is OK."""
+        writers = np.ascontiguousarray(writers, dtype=abi.SEG_WRITER_DTYPE)
+        entries = np.ascontiguousarray(entries, dtype=abi.SEG_ENTRY_DTYPE)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if pieces is None or out is None:
+            out_bound, pieces_bound = segment_flush_bound(writers, len(entries), len(data))
+            pieces = np.zeros(pieces_bound, dtype=abi.SEG_PIECE_DTYPE) if pieces is None else pieces
+            out = np.zeros(out_bound, dtype=np.uint8) if out is None else out
+        res = np.zeros(1, dtype=abi.SEG_FLUSH_RESULT_DTYPE)
+        self._check(self._L.rgb_segment_flush(self._h, writers.ctypes.data if len(writers) else None, len(writers),
+                                              entries.ctypes.data if len(entries) else None, len(entries),
+                                              data.ctypes.data if len(data) else None, len(data), max_count, max_size,
+                                              flags, pieces.ctypes.data if len(pieces) else None, len(pieces),
+                                              out.ctypes.data if len(out) else None, len(out), res.ctypes.data),
+                    "rgb_segment_flush")
+        if int(res["status"][0]) != abi.SEG_FLUSH_OK:
+            return res[0], None, None
+        return res[0], pieces[:int(res["n_pieces"][0])], out[:int(res["out_bytes"][0])]
+
     # -- observability -----------------------------------------------------------------
     def snapshot(self) -> np.ndarray:
         rows = np.zeros(self.n_groups, dtype=abi.LEADERBOARD_DTYPE)
@@ -883,6 +927,18 @@ def segment_compact_bound(sources, live, files_bytes: int):
     if rc != 0:
         raise RgbError(rc, "rgb_segment_compact_bound")
     return int(bound.value), int(max_count.value)
+
+
+def segment_flush_bound(writers, n_entries: int, data_bytes: int):
+    """(bytes of `out`, piece rows) that always suffice for a flush call -- host helper, no device work;
+    RgbError(RGB_E_INVAL) for malformed writers, as the flush calls answer them."""
+    writers = np.ascontiguousarray(writers, dtype=abi.SEG_WRITER_DTYPE)
+    out_bound, pieces_bound = C.c_uint64(0), C.c_uint32(0)
+    rc = lib().rgb_segment_flush_bound(writers.ctypes.data if len(writers) else None, len(writers), n_entries,
+                                       data_bytes, C.byref(out_bound), C.byref(pieces_bound))
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_flush_bound")
+    return int(out_bound.value), int(pieces_bound.value)
 
 
 def segment_scan(file_bytes, cap: int | None = None):
