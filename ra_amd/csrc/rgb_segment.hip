@@ -222,10 +222,45 @@ __device__ __forceinline__ u32 crc_bytes(const u32 *t0, u32 crc, const unsigned 
   return ~crc;
 }
 
+/* The CRC of one entry's payload of 16 bytes or more by the GROUP lanes that share it, valid on the group's first lane.
+ * Every lane of the group comes here, live or not (the butterfly needs them all); an entry that is not live, or
+ * shorter, is not read.  COPY: the payload goes to dst as it is read. */
+template <int GROUP, bool COPY>
+__device__ __forceinline__ u32 entry_crc(const u32 *lds, const unsigned char *pay, unsigned char *dst, u32 len, bool live,
+                                         u32 lane) {
+  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
+  const bool wide = live && len >= 16u;
+  const u32 part = lane_raw<GROUP, UNROLL, COPY>(lds, pay, dst, wide ? len : 0u, lane, 0xFFFFFFFFu);
+  return ~group_xor<GROUP>(part);
+}
+/* ... and the answer, on the first lane of a live entry: payloads under 16 bytes go byte by byte here, inside the
+ * caller's own lane-0 region (a region of their own in front of it costs the 8-lane build 3 to 5 % at 256-byte payloads) */
+template <bool COPY>
+__device__ __forceinline__ u32 lane0_crc(const u32 *lds, u32 group_crc, const unsigned char *pay, unsigned char *dst, u32 len) {
+  return len >= 16u ? group_crc : crc_bytes(lds, 0u, pay, len, COPY ? dst : nullptr);
+}
+
+/* <<"RASG", 2:16, MaxCount:16>> (src/ra_log_segment.erl:1118-1122) */
+__device__ __forceinline__ void put_header(unsigned char *at, u32 max_count) {
+  struct __attribute__((packed)) hdr8 { u64 v; } h;
+  h.v = 0x47534152ull | (0x0200ull << 32) | ((u64)((max_count >> 8) & 0xFFu) << 48) | ((u64)(max_count & 0xFFu) << 56);
+  __builtin_memcpy(at, &h, 8);
+}
+/* <<Idx:64, Term:64, DataOffset:64, Length:32, Crc:32>> (src/ra_log_segment.erl:1211-1219), at any alignment */
+__device__ __forceinline__ void put_record(unsigned char *rec, u64 idx, u64 term, u64 off, u32 len, u32 crc) {
+  v4u a, b;
+  a.x = __builtin_bswap32((u32)(idx >> 32));  a.y = __builtin_bswap32((u32)idx);
+  a.z = __builtin_bswap32((u32)(term >> 32)); a.w = __builtin_bswap32((u32)term);
+  b.x = __builtin_bswap32((u32)(off >> 32));  b.y = __builtin_bswap32((u32)off);
+  b.z = __builtin_bswap32(len);               b.w = __builtin_bswap32(crc);
+  *reinterpret_cast<v4u_any *>(rec) = a;
+  *reinterpret_cast<v4u_any *>(rec + 16) = b;
+}
+
 /* ---- per-entry CRC, and the segment image around it ------------------------------------------------------
  * GROUP lanes per entry (8 up to a mean payload of 320 bytes, 16 up to 1 KiB, then a wavefront), as the WAL kernels.
  * BUILD: the payload is copied to out + out_offsets[e] as it is read, the group's first lane writes the index record
- * <<Idx:64, Term:64, DataOffset:64, Length:32, Crc:32>> at 8 + 32 e, and the first thread of the grid the file header.
+ * at 8 + 32 e, and the first thread of the grid the file header.
  * An entry whose payload does not lie inside the data buffer, or whose copy does not lie inside the output, is not
  * touched at all (the host-buffer forms refuse such a batch before anything is launched). */
 template <int GROUP, bool BUILD>
@@ -236,14 +271,8 @@ __global__ __launch_bounds__(THREADS) void rgb_seg_crc_kernel(
   __shared__ __attribute__((aligned(16))) u32 lds[LDS_WORDS];
   load_tables<GROUP>(lds);
   constexpr u32 PER_BLOCK = THREADS / GROUP;
-  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
   const u32 lane = threadIdx.x & (GROUP - 1);
-  if (BUILD && blockIdx.x == 0 && threadIdx.x == 0) {
-    /* <<"RASG", 2:16, MaxCount:16>> (src/ra_log_segment.erl:1118-1122) */
-    struct __attribute__((packed)) hdr8 { u64 v; } h;
-    h.v = 0x47534152ull | (0x0200ull << 32) | ((u64)((max_count >> 8) & 0xFFu) << 48) | ((u64)(max_count & 0xFFu) << 56);
-    __builtin_memcpy(out, &h, 8);
-  }
+  if (BUILD && blockIdx.x == 0 && threadIdx.x == 0) put_header(out, max_count);
   for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
     const u32 e = base + threadIdx.x / GROUP;
     bool live = e < n;
@@ -257,21 +286,12 @@ __global__ __launch_bounds__(THREADS) void rgb_seg_crc_kernel(
     if (BUILD && (dst_off > out_bytes || len > out_bytes - dst_off)) live = false;
     const unsigned char *pay = data + en.data_offset;
     unsigned char *dst = BUILD ? out + dst_off : nullptr;
-    const bool wide = live && len >= 16u;
-    const u32 part = lane_raw<GROUP, UNROLL, BUILD>(lds, pay, dst, wide ? len : 0u, lane, 0xFFFFFFFFu);
-    u32 crc = ~group_xor<GROUP>(part);
+    u32 crc = entry_crc<GROUP, BUILD>(lds, pay, dst, len, live, lane);
     if (live && lane == 0u) {
-      if (!wide) crc = crc_bytes(lds, 0u, pay, len, dst);
+      crc = lane0_crc<BUILD>(lds, crc, pay, dst, len);
       if (BUILD) {
         if (flags & RGB_SEG_NO_CHECKSUMS) crc = 0u;
-        v4u a, b;
-        a.x = __builtin_bswap32((u32)(en.index >> 32)); a.y = __builtin_bswap32((u32)en.index);
-        a.z = __builtin_bswap32((u32)(en.term >> 32));  a.w = __builtin_bswap32((u32)en.term);
-        b.x = __builtin_bswap32((u32)(dst_off >> 32));  b.y = __builtin_bswap32((u32)dst_off);
-        b.z = __builtin_bswap32(len);                   b.w = __builtin_bswap32(crc);
-        unsigned char *rec = out + RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * e;
-        *reinterpret_cast<v4u_any *>(rec) = a;
-        *reinterpret_cast<v4u_any *>(rec + 16) = b;
+        put_record(out + RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * e, en.index, en.term, dst_off, len, crc);
       }
       if (crcs) crcs[e] = crc;
     }
@@ -600,14 +620,9 @@ __global__ __launch_bounds__(THREADS) void rgb_compact_copy_kernel(
   if (hdr->status != RGB_SEG_COMPACT_OK) return;        /* decided before this launch: the same for every lane */
   if (VERIFY) load_tables<GROUP>(lds);
   constexpr u32 PER_BLOCK = THREADS / GROUP;
-  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
   const u32 lane = threadIdx.x & (GROUP - 1);
   const u64 data_start = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * n;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    struct __attribute__((packed)) hdr8 { u64 v; } h;
-    h.v = 0x47534152ull | (0x0200ull << 32) | ((u64)((n >> 8) & 0xFFu) << 48) | ((u64)(n & 0xFFu) << 56);
-    __builtin_memcpy(out, &h, 8);
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) put_header(out, n);
   for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
     const u32 e = base + threadIdx.x / GROUP;
     const bool live = e < n;
@@ -619,26 +634,14 @@ __global__ __launch_bounds__(THREADS) void rgb_compact_copy_kernel(
     unsigned char *dst = out + dst_off;
     const bool wide = live && len >= 16u;
     u32 crc = 0;
-    if (VERIFY) {
-      const u32 part = lane_raw<GROUP, UNROLL, true>(lds, pay, dst, wide ? len : 0u, lane, 0xFFFFFFFFu);
-      crc = ~group_xor<GROUP>(part);
-    } else if (wide) {
-      copy_plain<GROUP>(pay, dst, len, lane);
-    }
+    if (VERIFY) crc = entry_crc<GROUP, true>(lds, pay, dst, len, live, lane);
+    else if (wide) copy_plain<GROUP>(pay, dst, len, lane);
     if (live && lane == 0u) {
-      if (!wide) {
-        if (VERIFY) crc = crc_bytes(lds, 0u, pay, len, dst);
-        else for (u32 k = 0; k < len; ++k) dst[k] = pay[k];
-      }
+      if (VERIFY) crc = lane0_crc<true>(lds, crc, pay, dst, len);
+      else if (!wide) for (u32 k = 0; k < len; ++k) dst[k] = pay[k];
       if (VERIFY && p.crc != 0u && crc != p.crc) atomic_min(&hdr->crc_fail, e);
-      v4u a, b;
-      a.x = __builtin_bswap32((u32)(p.idx >> 32));   a.y = __builtin_bswap32((u32)p.idx);
-      a.z = __builtin_bswap32((u32)(p.term >> 32));  a.w = __builtin_bswap32((u32)p.term);
-      b.x = __builtin_bswap32((u32)(dst_off >> 32)); b.y = __builtin_bswap32((u32)dst_off);
-      b.z = __builtin_bswap32(len);                  b.w = __builtin_bswap32(p.crc);      /* the source's Crc, 0 included */
-      unsigned char *rec = out + RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * e;
-      *reinterpret_cast<v4u_any *>(rec) = a;
-      *reinterpret_cast<v4u_any *>(rec + 16) = b;
+      /* the source's Crc, 0 included */
+      put_record(out + RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * e, p.idx, p.term, dst_off, len, p.crc);
     }
   }
 }
@@ -949,11 +952,7 @@ __global__ __launch_bounds__(THREADS) void rgb_flush_place_kernel(
     d.writer = p.writer; d._pad = 0u;
     *reinterpret_cast<fl_place *>(plan + e) = d;
     if (e == p.start) {
-      if (!open_file) {                                 /* <<"RASG", 2:16, MaxCount:16>> */
-        struct __attribute__((packed)) hdr8 { u64 v; } h;
-        h.v = 0x47534152ull | (0x0200ull << 32) | ((u64)((max_count >> 8) & 0xFFu) << 48) | ((u64)(max_count & 0xFFu) << 56);
-        __builtin_memcpy(out + piece_off, &h, 8);
-      }
+      if (!open_file) put_header(out + piece_off, max_count);
       rgb_seg_piece row;
       row.writer = p.writer; row.ordinal = p.ordinal; row.entry_first = e; row.entry_n = pc.entry_n;
       row.index_file_off = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * in_file;
@@ -974,7 +973,6 @@ __global__ __launch_bounds__(THREADS) void rgb_flush_copy_kernel(
   if (hdr->status != RGB_SEG_FLUSH_OK) return;          /* decided before this launch: the same for every lane */
   load_tables<GROUP>(lds);
   constexpr u32 PER_BLOCK = THREADS / GROUP;
-  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
   const u32 lane = threadIdx.x & (GROUP - 1);
   for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
     const u32 e = base + threadIdx.x / GROUP;
@@ -986,20 +984,11 @@ __global__ __launch_bounds__(THREADS) void rgb_flush_copy_kernel(
     const u32 len = en.len;
     const unsigned char *pay = data + en.off;
     unsigned char *dst = out + d.dst_off;
-    const bool wide = live && len >= 16u;
-    const u32 part = lane_raw<GROUP, UNROLL, true>(lds, pay, dst, wide ? len : 0u, lane, 0xFFFFFFFFu);
-    u32 crc = ~group_xor<GROUP>(part);
+    u32 crc = entry_crc<GROUP, true>(lds, pay, dst, len, live, lane);
     if (live && lane == 0u) {
-      if (!wide) crc = crc_bytes(lds, 0u, pay, len, dst);
+      crc = lane0_crc<true>(lds, crc, pay, dst, len);
       if (flags & RGB_SEG_NO_CHECKSUMS) crc = 0u;
-      v4u a, b;
-      a.x = __builtin_bswap32((u32)(en.idx >> 32));     a.y = __builtin_bswap32((u32)en.idx);
-      a.z = __builtin_bswap32((u32)(en.term >> 32));    a.w = __builtin_bswap32((u32)en.term);
-      b.x = __builtin_bswap32((u32)(d.file_off >> 32)); b.y = __builtin_bswap32((u32)d.file_off);
-      b.z = __builtin_bswap32(len);                     b.w = __builtin_bswap32(crc);
-      unsigned char *rec = out + d.rec_off;
-      *reinterpret_cast<v4u_any *>(rec) = a;
-      *reinterpret_cast<v4u_any *>(rec + 16) = b;
+      put_record(out + d.rec_off, en.idx, en.term, d.file_off, len, crc);
     }
   }
 }
@@ -1007,84 +996,154 @@ __global__ __launch_bounds__(THREADS) void rgb_flush_copy_kernel(
 /* x^(8 n) mod P on the host */
 inline u32 host_xpow8(u64 n) { return xpow8_c(n); }
 
-inline bool slice_ok(uint64_t off, uint64_t len, uint64_t bytes) { return off <= bytes && len <= bytes - off; }
-
 }  // namespace seg
 }  // namespace
 
 extern "C" void *rgb_ctx_stream(rgb_ctx *ctx);
 extern "C" int rgb_ctx_device(rgb_ctx *ctx);
 
-/* ---- per-context device buffers: staging of the host-buffer forms, partial values of the stream form ---- */
 #include <string.h>
 #include <mutex>
-#include <memory>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 namespace {
 namespace seg {
+
+/* ---- launching the per-entry kernels -------------------------------------------------------------------- */
+
+/* the lanes that share an entry, from the mean payload of the call: known to the host without a sync, and a wrong guess
+ * costs speed, never correctness */
+inline u32 group_width(u64 mean_bytes) { return mean_bytes <= 320u ? 8u : mean_bytes < 1024u ? 16u : 64u; }
+/* workgroups for n entries of `width` lanes each: capped (the kernels walk the batch), never 0 */
+inline u32 entry_grid(u32 n, u32 width) {
+  const u32 per = THREADS / width, grid = (n + per - 1u) / per;
+  return grid > GRID_CAP ? GRID_CAP : grid ? grid : 1u;
+}
+/* f(std::integral_constant<int, width>), for the three widths the kernels are built for */
+template <class F>
+inline void with_width(u32 width, F &&f) {
+  if (width == 8u) f(std::integral_constant<int, 8>{});
+  else if (width == 16u) f(std::integral_constant<int, 16>{});
+  else f(std::integral_constant<int, 64>{});
+}
+
+/* ---- per-context device buffers: staging of the host-buffer forms, scratch of the device forms ---------- */
+
+/* a device block that only ever grows; gone with the context */
+struct dev_buf {
+  void *p = nullptr;
+  size_t cap = 0;
+  dev_buf() = default;
+  dev_buf(const dev_buf &) = delete;
+  dev_buf &operator=(const dev_buf &) = delete;
+  ~dev_buf() { if (p) (void)hipFree(p); }
+  int reserve(size_t need) {
+    if (need <= cap) return 0;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = need + need / 2 + 4096;
+    if (hipMalloc(&p, want) != hipSuccess) return -1;
+    cap = want;
+    return 0;
+  }
+};
+
+/* The descriptors of a device-form call on their way up: the host fills the pinned block `h`, `d` is its device copy.
+ * `done` is recorded behind the upload, and the next call waits for it before it refills `h`. */
+struct pinned_upload {
+  void *h = nullptr;
+  size_t cap_h = 0;
+  dev_buf d;
+  hipEvent_t done = nullptr;
+  bool recorded = false;
+  ~pinned_upload() {
+    if (h) (void)hipHostFree(h);
+    if (done) (void)hipEventDestroy(done);
+  }
+  /* the previous upload is over, and the pinned side holds `need` bytes: nothing on the device is touched yet, so
+   * the caller can still validate (into `h`) and refuse */
+  int prepare(size_t need) {
+    if (!done && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return RGB_E_HIP;
+    if (recorded && hipEventSynchronize(done) != hipSuccess) return RGB_E_HIP;
+    recorded = false;
+    if (need > cap_h) {
+      if (h) (void)hipHostFree(h);
+      h = nullptr; cap_h = 0;
+      if (hipHostMalloc(&h, need * 2u, hipHostMallocDefault) != hipSuccess) return RGB_E_NOMEM;
+      cap_h = need * 2u;
+    }
+    return RGB_OK;
+  }
+  int upload(size_t need, hipStream_t st) {
+    if (d.reserve(need)) return RGB_E_NOMEM;
+    if (hipMemcpyAsync(d.p, h, need, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+    if (hipEventRecord(done, st) != hipSuccess) return RGB_E_HIP;
+    recorded = true;
+    return RGB_OK;
+  }
+};
+
 struct stage {
-  void *d_entries = nullptr, *d_data = nullptr, *d_crcs = nullptr, *d_offsets = nullptr, *d_out = nullptr;
-  size_t cap_e = 0, cap_d = 0, cap_c = 0, cap_o = 0, cap_out = 0;
-  void *d_partials = nullptr;     /* STREAM_MAX_BLOCKS values + the one result of the host-buffer form */
-  /* compaction: the descriptors of a call (pinned, and their device copy), the scratch plan, the result of the
-   * host-buffer form; `staged` is recorded behind the upload, the next call waits for it before it refills h_desc */
-  void *h_desc = nullptr, *d_desc = nullptr, *d_work = nullptr, *d_result = nullptr;
-  size_t cap_hdesc = 0, cap_desc = 0, cap_work = 0, cap_result = 0;
-  hipEvent_t staged = nullptr;
-  bool staged_recorded = false;
-  /* mem-table flush: the writers of a call (pinned, and their device copy), the scratch plan, and for the host-buffer
-   * form the piece rows and the result; fl_staged as `staged` */
-  void *h_fl = nullptr, *d_fl = nullptr, *d_fl_work = nullptr, *d_fl_pieces = nullptr, *d_fl_result = nullptr;
-  size_t cap_hfl = 0, cap_fl = 0, cap_fl_work = 0, cap_fl_pieces = 0, cap_fl_result = 0;
-  hipEvent_t fl_staged = nullptr;
-  bool fl_recorded = false;
+  dev_buf entries, data, offsets;                     /* host-buffer forms: what goes up ... */
+  dev_buf crcs, out, pieces, result;                  /* ... and what comes down */
+  dev_buf partials;                                   /* STREAM_MAX_BLOCKS values + the one result of the host-buffer form */
+  pinned_upload compact_desc, flush_writers;          /* device forms: the host arrays of a call ... */
+  dev_buf compact_work, flush_work;                   /* ... and its scratch plan */
 };
 std::recursive_mutex g_mu;     /* the host-buffer forms call the device forms with it held */
-std::unordered_map<rgb_ctx *, stage> g_stages;
-int grow(void **p, size_t *cap, size_t need) {
-  if (need <= *cap) return 0;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const size_t want = need + need / 2 + 4096;
-  if (hipMalloc(p, want) != hipSuccess) return -1;
-  *cap = want;
-  return 0;
-}
+/* never destroyed: a context that is still open when the process ends must not free through a runtime that is gone */
+std::unordered_map<rgb_ctx *, stage> &g_stages = *new std::unordered_map<rgb_ctx *, stage>;
+
 /* the partial values of the context (allocated on the first long buffer) */
 u32 *partials_of(rgb_ctx *ctx) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   stage &s = g_stages[ctx];
-  if (!s.d_partials && hipMalloc(&s.d_partials, (size_t)(STREAM_MAX_BLOCKS + 1u) * sizeof(u32)) != hipSuccess)
-    s.d_partials = nullptr;
-  return (u32 *)s.d_partials;
+  if (s.partials.reserve((size_t)(STREAM_MAX_BLOCKS + 1u) * sizeof(u32))) return nullptr;
+  return (u32 *)s.partials.p;
+}
+
+/* ---- the steps of a host-buffer form: stage the inputs, call the device form, fetch the answer ---------- */
+
+inline bool slices_ok(const rgb_seg_entry *entries, u32 n, uint64_t data_bytes) {
+  for (u32 i = 0; i < n; ++i)
+    if (entries[i].data_offset > data_bytes || entries[i].data_len > data_bytes - entries[i].data_offset) return false;
+  return true;
+}
+/* room for `bytes` in b, and the host's bytes in it */
+int stage_in(dev_buf &b, const void *src, size_t bytes, hipStream_t st) {
+  if (b.reserve(bytes)) return RGB_E_NOMEM;
+  if (bytes && hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  return RGB_OK;
+}
+int copy_down(void *dst, const dev_buf &b, size_t bytes, hipStream_t st) {
+  return bytes && hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess ? RGB_E_HIP : RGB_OK;
+}
+/* ... and the call is over */
+int fetch(void *dst, const dev_buf &b, size_t bytes, hipStream_t st) {
+  if (copy_down(dst, b, bytes, st)) return RGB_E_HIP;
+  return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+/* The result row first; only the status `ok` brings the bulk bytes back, which bulk(row) enqueues: the caller's buffers
+ * stay untouched otherwise. */
+template <class Row, class F>
+int fetch_result(Row *result, const dev_buf &d_row, u32 ok, hipStream_t st, F &&bulk) {
+  Row row;
+  if (int rc = fetch(&row, d_row, sizeof row, st)) return rc;
+  if (row.status == ok) {
+    if (int rc = bulk(row)) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  }
+  *result = row;
+  return RGB_OK;
 }
 }  // namespace seg
 }  // namespace
 
 extern "C" void rgb_seg_release(rgb_ctx *ctx) {      /* called by rgb_close */
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
-  auto it = seg::g_stages.find(ctx);
-  if (it == seg::g_stages.end()) return;
-  seg::stage &s = it->second;
-  void *all[] = {s.d_entries, s.d_data, s.d_crcs, s.d_offsets, s.d_out, s.d_partials, s.d_desc, s.d_work, s.d_result,
-                 s.d_fl, s.d_fl_work, s.d_fl_pieces, s.d_fl_result};
-  for (void *p : all) if (p) (void)hipFree(p);
-  if (s.h_desc) (void)hipHostFree(s.h_desc);
-  if (s.h_fl) (void)hipHostFree(s.h_fl);
-  if (s.staged) (void)hipEventDestroy(s.staged);
-  if (s.fl_staged) (void)hipEventDestroy(s.fl_staged);
-  seg::g_stages.erase(it);
+  seg::g_stages.erase(ctx);
 }
-
-#define SEG_LAUNCH(G, BUILD, ...)                                                                                    \
-  do {                                                                                                               \
-    const seg::u32 per = seg::THREADS / (G);                                                                         \
-    seg::u32 grid = (n + per - 1) / per;                                                                             \
-    if (grid > seg::GRID_CAP) grid = seg::GRID_CAP;                                                                  \
-    if (grid == 0) grid = 1;                                                                                         \
-    hipLaunchKernelGGL((seg::rgb_seg_crc_kernel<G, BUILD>), dim3(grid), dim3(seg::THREADS), 0, st, __VA_ARGS__);     \
-  } while (0)
 
 extern "C" int rgb_crc32_device(rgb_ctx *ctx, const void *d_entries, uint32_t n, const void *d_data,
                                 uint64_t data_bytes, void *d_crcs, void *stream) {
@@ -1092,13 +1151,13 @@ extern "C" int rgb_crc32_device(rgb_ctx *ctx, const void *d_entries, uint32_t n,
   if (n == 0) return RGB_OK;
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
   (void)hipGetLastError();
-  const uint64_t mean = data_bytes / n;
-#define SEG_CRC_ARGS (const rgb_seg_entry *)d_entries, n, (const unsigned char *)d_data, data_bytes, (seg::u32 *)d_crcs, \
-                     (unsigned char *)nullptr, (seg::u64)0, (const seg::u64 *)nullptr, 0u, 0u
-  if (mean <= 320u) SEG_LAUNCH(8, false, SEG_CRC_ARGS);
-  else if (mean < 1024u) SEG_LAUNCH(16, false, SEG_CRC_ARGS);
-  else SEG_LAUNCH(64, false, SEG_CRC_ARGS);
-#undef SEG_CRC_ARGS
+  const seg::u32 width = seg::group_width(data_bytes / n);
+  seg::with_width(width, [&](auto g) {
+    hipLaunchKernelGGL((seg::rgb_seg_crc_kernel<decltype(g)::value, false>), dim3(seg::entry_grid(n, width)),
+                       dim3(seg::THREADS), 0, st, (const rgb_seg_entry *)d_entries, n, (const unsigned char *)d_data,
+                       data_bytes, (seg::u32 *)d_crcs, (unsigned char *)nullptr, (seg::u64)0, (const seg::u64 *)nullptr,
+                       0u, 0u);
+  });
   return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
 }
 
@@ -1116,16 +1175,15 @@ extern "C" int rgb_segment_build_device(rgb_ctx *ctx, const void *d_entries, uin
       hipMemsetAsync((unsigned char *)d_out + RGB_SEG_HEADER_BYTES + (uint64_t)RGB_SEG_RECORD_BYTES * n, 0,
                      (uint64_t)RGB_SEG_RECORD_BYTES * (max_count - n), st) != hipSuccess)
     return RGB_E_HIP;
-  const uint64_t mean = n ? data_bytes / n : 0;
-#define SEG_BUILD_ARGS (const rgb_seg_entry *)d_entries, n, (const unsigned char *)d_data, data_bytes, (seg::u32 *)nullptr, \
-                       (unsigned char *)d_out, (seg::u64)out_bytes, (const seg::u64 *)d_out_offsets, max_count, flags
-  if (mean <= 320u) SEG_LAUNCH(8, true, SEG_BUILD_ARGS);
-  else if (mean < 1024u) SEG_LAUNCH(16, true, SEG_BUILD_ARGS);
-  else SEG_LAUNCH(64, true, SEG_BUILD_ARGS);
-#undef SEG_BUILD_ARGS
+  const seg::u32 width = seg::group_width(n ? data_bytes / n : 0);
+  seg::with_width(width, [&](auto g) {
+    hipLaunchKernelGGL((seg::rgb_seg_crc_kernel<decltype(g)::value, true>), dim3(seg::entry_grid(n, width)),
+                       dim3(seg::THREADS), 0, st, (const rgb_seg_entry *)d_entries, n, (const unsigned char *)d_data,
+                       data_bytes, (seg::u32 *)nullptr, (unsigned char *)d_out, (seg::u64)out_bytes,
+                       (const seg::u64 *)d_out_offsets, max_count, flags);
+  });
   return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
 }
-#undef SEG_LAUNCH
 
 extern "C" int rgb_crc32_stream_device(rgb_ctx *ctx, const void *d_data, uint64_t n_bytes, uint32_t init,
                                        void *d_crc, void *stream) {
@@ -1164,22 +1222,19 @@ extern "C" int rgb_crc32(rgb_ctx *ctx, const rgb_seg_entry *entries, uint32_t n,
                          uint64_t data_bytes, uint32_t *crcs) {
   if (!ctx || (n && (!entries || !crcs)) || (data_bytes && !data)) return RGB_E_INVAL;
   if (n == 0) return RGB_OK;
-  for (uint32_t i = 0; i < n; ++i)
-    if (!seg::slice_ok(entries[i].data_offset, entries[i].data_len, data_bytes)) return RGB_E_INVAL;
+  if (!seg::slices_ok(entries, n, data_bytes)) return RGB_E_INVAL;
   if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
   seg::stage &s = seg::g_stages[ctx];
-  const size_t need_e = (size_t)n * sizeof(rgb_seg_entry);
-  if (seg::grow(&s.d_entries, &s.cap_e, need_e) || seg::grow(&s.d_crcs, &s.cap_c, (size_t)n * 4u) ||
-      seg::grow(&s.d_data, &s.cap_d, (size_t)data_bytes))
-    return RGB_E_NOMEM;
   hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
-  if (hipMemcpyAsync(s.d_entries, entries, need_e, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  if (data_bytes && hipMemcpyAsync(s.d_data, data, data_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  int rc = rgb_crc32_device(ctx, s.d_entries, n, s.d_data, data_bytes, s.d_crcs, st);
+  if (s.crcs.reserve((size_t)n * 4u)) return RGB_E_NOMEM;
+  int rc;
+  if ((rc = seg::stage_in(s.entries, entries, (size_t)n * sizeof(rgb_seg_entry), st)) ||
+      (rc = seg::stage_in(s.data, data, (size_t)data_bytes, st)))
+    return rc;
+  rc = rgb_crc32_device(ctx, s.entries.p, n, s.data.p, data_bytes, s.crcs.p, st);
   if (rc) return rc;
-  if (hipMemcpyAsync(crcs, s.d_crcs, (size_t)n * 4u, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+  return seg::fetch(crcs, s.crcs, (size_t)n * 4u, st);
 }
 
 extern "C" int rgb_crc32_stream(rgb_ctx *ctx, const void *data, uint64_t n_bytes, uint32_t init, uint32_t *crc_out) {
@@ -1189,11 +1244,11 @@ extern "C" int rgb_crc32_stream(rgb_ctx *ctx, const void *data, uint64_t n_bytes
   seg::u32 *partials = seg::partials_of(ctx);
   if (!partials) return RGB_E_NOMEM;
   seg::stage &s = seg::g_stages[ctx];
-  if (seg::grow(&s.d_data, &s.cap_d, (size_t)n_bytes)) return RGB_E_NOMEM;
   hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
-  if (n_bytes && hipMemcpyAsync(s.d_data, data, n_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
+  int rc = seg::stage_in(s.data, data, (size_t)n_bytes, st);
+  if (rc) return rc;
   seg::u32 *d_crc = partials + seg::STREAM_MAX_BLOCKS;
-  int rc = rgb_crc32_stream_device(ctx, s.d_data, n_bytes, init, d_crc, st);
+  rc = rgb_crc32_stream_device(ctx, s.data.p, n_bytes, init, d_crc, st);
   if (rc) return rc;
   if (hipMemcpyAsync(crc_out, d_crc, 4u, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
   return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
@@ -1203,28 +1258,25 @@ extern "C" int rgb_segment_build(rgb_ctx *ctx, const rgb_seg_entry *entries, uin
                                  const void *data, uint64_t data_bytes, void *out, uint64_t out_bytes, uint32_t flags) {
   if (!ctx || !out || (n && !entries) || (data_bytes && !data) || (flags & ~RGB_SEG_NO_CHECKSUMS)) return RGB_E_INVAL;
   if (n > max_count || max_count > 65535u) return RGB_E_INVAL;
-  for (uint32_t i = 0; i < n; ++i)
-    if (!seg::slice_ok(entries[i].data_offset, entries[i].data_len, data_bytes)) return RGB_E_INVAL;
+  if (!seg::slices_ok(entries, n, data_bytes)) return RGB_E_INVAL;
   std::vector<uint64_t> offs(n ? n : 1);
   const uint64_t total = rgb_segment_layout(entries, n, max_count, offs.data());
   if (out_bytes < total) return RGB_E_INVAL;
   if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
   seg::stage &s = seg::g_stages[ctx];
-  const size_t need_e = (size_t)n * sizeof(rgb_seg_entry);
-  if (seg::grow(&s.d_entries, &s.cap_e, need_e) || seg::grow(&s.d_offsets, &s.cap_o, (size_t)n * 8u) ||
-      seg::grow(&s.d_data, &s.cap_d, (size_t)data_bytes) || seg::grow(&s.d_out, &s.cap_out, (size_t)total))
-    return RGB_E_NOMEM;
   hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
-  if (n && hipMemcpyAsync(s.d_entries, entries, need_e, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  if (n && hipMemcpyAsync(s.d_offsets, offs.data(), (size_t)n * 8u, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  if (data_bytes && hipMemcpyAsync(s.d_data, data, data_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  int rc = rgb_segment_build_device(ctx, s.d_entries, n, max_count, s.d_offsets, s.d_data, data_bytes, s.d_out, total,
-                                    flags, st);
+  if (s.out.reserve((size_t)total)) return RGB_E_NOMEM;
+  int rc;
+  if ((rc = seg::stage_in(s.entries, entries, (size_t)n * sizeof(rgb_seg_entry), st)) ||
+      (rc = seg::stage_in(s.offsets, offs.data(), (size_t)n * 8u, st)) ||
+      (rc = seg::stage_in(s.data, data, (size_t)data_bytes, st)))
+    return rc;
+  rc = rgb_segment_build_device(ctx, s.entries.p, n, max_count, s.offsets.p, s.data.p, data_bytes, s.out.p, total, flags,
+                                st);
   if (rc) return rc;
   /* only the file's own bytes come back: `out` behind them is the caller's */
-  if (hipMemcpyAsync(out, s.d_out, total, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+  return seg::fetch(out, s.out, (size_t)total, st);
 }
 
 /* validate_checksum/2 (src/ra_log_segment.erl:1245-1248) over the records of a scanned file, in order */
@@ -1269,23 +1321,17 @@ int stage_call(stage &s, const rgb_seg_source *sources, u32 n_sources, const uin
   const size_t off_live = (size_t)n_sources * sizeof(src_desc);
   const size_t off_rank = off_live + (size_t)n_live * 16u;
   const size_t need = up16(off_rank + (size_t)n_live * 4u) + 16u;
-  if (!s.staged && hipEventCreateWithFlags(&s.staged, hipEventDisableTiming) != hipSuccess) return RGB_E_HIP;
-  if (s.staged_recorded && hipEventSynchronize(s.staged) != hipSuccess) return RGB_E_HIP;
-  s.staged_recorded = false;
-  if (need > s.cap_hdesc) {
-    if (s.h_desc) (void)hipHostFree(s.h_desc);
-    s.h_desc = nullptr; s.cap_hdesc = 0;
-    if (hipHostMalloc(&s.h_desc, need * 2u, hipHostMallocDefault) != hipSuccess) return RGB_E_NOMEM;
-    s.cap_hdesc = need * 2u;
-  }
-  unsigned char *h = (unsigned char *)s.h_desc;
+  pinned_upload &up = s.compact_desc;
+  int rc = up.prepare(need);                            /* (the check leaves the ranks in the pinned block) */
+  if (rc) return rc;
+  unsigned char *h = (unsigned char *)up.h;
   src_desc *h_srcs = (src_desc *)h;
   u32 *h_rank = (u32 *)(h + off_rank);
   uint32_t asked[RGB_SEG_COMPACT_MAX_SOURCES];
   uint32_t max_count = 0;
   uint64_t sum = 0;
-  const int rc = rgb_seg_compact_check(sources, n_sources, live, n_live, files_bytes, with_live ? 1 : 0, compact ? 1 : 0,
-                                       asked, h_rank, &sum, &max_count);
+  rc = rgb_seg_compact_check(sources, n_sources, live, n_live, files_bytes, with_live ? 1 : 0, compact ? 1 : 0, asked,
+                             h_rank, &sum, &max_count);
   if (rc) return rc;
   u32 plan_base = 0;
   for (u32 i = 0; i < n_sources; ++i) {
@@ -1300,12 +1346,9 @@ int stage_call(stage &s, const rgb_seg_source *sources, u32 n_sources, const uin
   const size_t off_base = (size_t)n_sources * sizeof(src_done);
   const size_t off_hdr = up16(off_base + (size_t)n_sources * 8u);
   const size_t off_plan = off_hdr + sizeof(work_hdr);
-  if (grow(&s.d_desc, &s.cap_desc, need) || grow(&s.d_work, &s.cap_work, off_plan + (size_t)max_count * sizeof(plan_rec) + 16u))
-    return RGB_E_NOMEM;
-  if (hipMemcpyAsync(s.d_desc, s.h_desc, need, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  if (hipEventRecord(s.staged, st) != hipSuccess) return RGB_E_HIP;
-  s.staged_recorded = true;
-  unsigned char *d = (unsigned char *)s.d_desc, *w = (unsigned char *)s.d_work;
+  if (s.compact_work.reserve(off_plan + (size_t)max_count * sizeof(plan_rec) + 16u)) return RGB_E_NOMEM;
+  if ((rc = up.upload(need, st))) return rc;
+  unsigned char *d = (unsigned char *)up.d.p, *w = (unsigned char *)s.compact_work.p;
   out->d_srcs = (const src_desc *)d;
   out->d_live = (const u64 *)(d + off_live);
   out->d_rank = (const u32 *)(d + off_rank);
@@ -1372,33 +1415,20 @@ extern "C" int rgb_segment_compact_device(rgb_ctx *ctx, const rgb_seg_source *so
   hipLaunchKernelGGL(seg::rgb_compact_place_kernel, dim3(1), dim3(64), 0, st, c.d_srcs, n_sources,
                      (const seg::src_done *)c.d_done, (const seg::plan_rec *)c.d_plan, c.max_count, (seg::u64)max_size,
                      (seg::u64)out_bytes, c.d_byte_base, c.d_hdr, d_result);
-  /* the lane-group width of rgb_segment_build_device, from what the host knows without a sync: a wrong guess costs
-   * speed, never correctness */
+  /* (the mean over the sources' bytes, not the live payloads': those are not known here) */
   const uint32_t n = c.max_count;
-  const uint64_t mean = c.sum_bytes / (n ? n : 1u);
+  const seg::u32 width = seg::group_width(c.sum_bytes / (n ? n : 1u));
   const bool verify = (flags & RGB_SEG_COMPACT_VERIFY) != 0u;
-#define SEG_COPY_LAUNCH(G, V)                                                                                        \
-  do {                                                                                                               \
-    const seg::u32 per = seg::THREADS / (G);                                                                         \
-    seg::u32 grid = (n + per - 1) / per;                                                                             \
-    if (grid > seg::GRID_CAP) grid = seg::GRID_CAP;                                                                  \
-    if (grid == 0) grid = 1;                                                                                         \
-    hipLaunchKernelGGL((seg::rgb_compact_copy_kernel<G, V>), dim3(grid), dim3(seg::THREADS), 0, st,                  \
-                       (const seg::plan_rec *)c.d_plan, n, (const unsigned char *)d_files,                           \
-                       (const seg::u64 *)c.d_byte_base, c.d_hdr, (unsigned char *)d_out);                            \
-  } while (0)
-  if (verify) {
-    if (mean <= 320u) SEG_COPY_LAUNCH(8, true);
-    else if (mean < 1024u) SEG_COPY_LAUNCH(16, true);
-    else SEG_COPY_LAUNCH(64, true);
+  seg::with_width(width, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    auto *copy = verify ? seg::rgb_compact_copy_kernel<G, true> : seg::rgb_compact_copy_kernel<G, false>;
+    hipLaunchKernelGGL(copy, dim3(seg::entry_grid(n, width)), dim3(seg::THREADS), 0, st, (const seg::plan_rec *)c.d_plan,
+                       n, (const unsigned char *)d_files, (const seg::u64 *)c.d_byte_base, c.d_hdr,
+                       (unsigned char *)d_out);
+  });
+  if (verify)
     hipLaunchKernelGGL(seg::rgb_compact_finish_kernel, dim3(1), dim3(64), 0, st, (const seg::plan_rec *)c.d_plan,
                        (const seg::work_hdr *)c.d_hdr, d_result);
-  } else {
-    if (mean <= 320u) SEG_COPY_LAUNCH(8, false);
-    else if (mean < 1024u) SEG_COPY_LAUNCH(16, false);
-    else SEG_COPY_LAUNCH(64, false);
-  }
-#undef SEG_COPY_LAUNCH
   return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
 }
 
@@ -1414,13 +1444,12 @@ extern "C" int rgb_segment_info(rgb_ctx *ctx, const rgb_seg_source *sources, uin
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
   seg::stage &s = seg::g_stages[ctx];
   const size_t need_i = (size_t)n_sources * sizeof(rgb_seg_info);
-  if (seg::grow(&s.d_data, &s.cap_d, (size_t)files_bytes) || seg::grow(&s.d_result, &s.cap_result, need_i)) return RGB_E_NOMEM;
   hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
-  if (files_bytes && hipMemcpyAsync(s.d_data, files, files_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  rc = rgb_segment_info_device(ctx, sources, n_sources, s.d_data, files_bytes, live, n_live, s.d_result, st);
+  if (s.result.reserve(need_i)) return RGB_E_NOMEM;
+  if ((rc = seg::stage_in(s.data, files, (size_t)files_bytes, st))) return rc;
+  rc = rgb_segment_info_device(ctx, sources, n_sources, s.data.p, files_bytes, live, n_live, s.result.p, st);
   if (rc) return rc;
-  if (hipMemcpyAsync(infos, s.d_result, need_i, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-  return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+  return seg::fetch(infos, s.result, need_i, st);
 }
 
 extern "C" int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *files,
@@ -1436,24 +1465,16 @@ extern "C" int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, 
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
   seg::stage &s = seg::g_stages[ctx];
   const uint64_t room = out_bytes < bound ? out_bytes : bound;         /* the image never needs more than the bound */
-  if (seg::grow(&s.d_data, &s.cap_d, (size_t)files_bytes) || seg::grow(&s.d_out, &s.cap_out, (size_t)room + 16u) ||
-      seg::grow(&s.d_result, &s.cap_result, sizeof(rgb_seg_compact_result)))
-    return RGB_E_NOMEM;
   hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
-  if (files_bytes && hipMemcpyAsync(s.d_data, files, files_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  rc = rgb_segment_compact_device(ctx, sources, n_sources, s.d_data, files_bytes, live, n_live, max_size, flags, s.d_out,
-                                  room, s.d_result, st);
+  if (s.out.reserve((size_t)room + 16u) || s.result.reserve(sizeof(rgb_seg_compact_result))) return RGB_E_NOMEM;
+  if ((rc = seg::stage_in(s.data, files, (size_t)files_bytes, st))) return rc;
+  rc = rgb_segment_compact_device(ctx, sources, n_sources, s.data.p, files_bytes, live, n_live, max_size, flags, s.out.p,
+                                  room, s.result.p, st);
   if (rc) return rc;
-  rgb_seg_compact_result res;
-  if (hipMemcpyAsync(&res, s.d_result, sizeof res, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-  if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
   /* only the image's own bytes come back, and only a good image */
-  if (res.status == RGB_SEG_COMPACT_OK) {
-    if (hipMemcpyAsync(out, s.d_out, res.file_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
-  }
-  *result = res;
-  return RGB_OK;
+  return seg::fetch_result(result, s.result, RGB_SEG_COMPACT_OK, st, [&](const rgb_seg_compact_result &res) {
+    return seg::copy_down(out, s.out, (size_t)res.file_bytes, st);
+  });
 }
 
 /* ---- mem-table flush: the entries of many writers into their segment files ------------------------------ */
@@ -1476,8 +1497,8 @@ extern "C" int rgb_segment_flush_device(rgb_ctx *ctx, const rgb_seg_writer *writ
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
   seg::stage &s = seg::g_stages[ctx];
   /* the sub-group of the plan, by the longest writer; every workgroup a whole number of steps of it */
-  const seg::u32 width = longest <= 8u ? 8u : longest <= 16u ? 16u : (seg::u32)seg::FL_CHUNK;
-  const seg::u32 subs = seg::THREADS / width;
+  const seg::u32 plan_width = longest <= 8u ? 8u : longest <= 16u ? 16u : (seg::u32)seg::FL_CHUNK;
+  const seg::u32 subs = seg::THREADS / plan_width;
   seg::u32 grid = (n_writers + subs - 1u) / subs;
   if (grid > seg::FL_GRID_CAP) grid = seg::FL_GRID_CAP;
   if (grid == 0u) grid = 1u;
@@ -1487,28 +1508,19 @@ extern "C" int rgb_segment_flush_device(rgb_ctx *ctx, const rgb_seg_writer *writ
   const seg::u32 n_blocks = (n_writers + per_block - 1u) / per_block;      /* 0 without writers */
   /* the writers, through the context's pinned buffer */
   const size_t need = (size_t)n_writers * sizeof(seg::fl_writer) + 16u;
-  if (!s.fl_staged && hipEventCreateWithFlags(&s.fl_staged, hipEventDisableTiming) != hipSuccess) return RGB_E_HIP;
-  if (s.fl_recorded && hipEventSynchronize(s.fl_staged) != hipSuccess) return RGB_E_HIP;
-  s.fl_recorded = false;
-  if (need > s.cap_hfl) {
-    if (s.h_fl) (void)hipHostFree(s.h_fl);
-    s.h_fl = nullptr; s.cap_hfl = 0;
-    if (hipHostMalloc(&s.h_fl, need * 2u, hipHostMallocDefault) != hipSuccess) return RGB_E_NOMEM;
-    s.cap_hfl = need * 2u;
-  }
-  if (n_writers) memcpy(s.h_fl, writers, (size_t)n_writers * sizeof(seg::fl_writer));
+  seg::pinned_upload &up = s.flush_writers;
+  if ((rc = up.prepare(need))) return rc;
+  if (n_writers) memcpy(up.h, writers, (size_t)n_writers * sizeof(seg::fl_writer));
   /* the scratch: a row per writer, the sums of the plan's workgroups, the status, a plan record and a piece per entry */
   const size_t off_tot = (size_t)n_writers * sizeof(seg::fl_row);
   const size_t off_hdr = off_tot + (size_t)seg::FL_GRID_CAP * sizeof(seg::fl_total);
   const size_t off_plan = off_hdr + sizeof(seg::work_hdr);
   const size_t off_pieces = off_plan + (size_t)n_entries * sizeof(seg::fl_plan);
   const size_t work = off_pieces + (size_t)n_entries * sizeof(seg::fl_piece) + 16u;
-  if (seg::grow(&s.d_fl, &s.cap_fl, need) || seg::grow(&s.d_fl_work, &s.cap_fl_work, work)) return RGB_E_NOMEM;
-  if (hipMemcpyAsync(s.d_fl, s.h_fl, need, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  if (hipEventRecord(s.fl_staged, st) != hipSuccess) return RGB_E_HIP;
-  s.fl_recorded = true;
-  unsigned char *w = (unsigned char *)s.d_fl_work;
-  const seg::fl_writer *d_writers = (const seg::fl_writer *)s.d_fl;
+  if (s.flush_work.reserve(work)) return RGB_E_NOMEM;
+  if ((rc = up.upload(need, st))) return rc;
+  unsigned char *w = (unsigned char *)s.flush_work.p;
+  const seg::fl_writer *d_writers = (const seg::fl_writer *)up.d.p;
   seg::fl_row *d_rows = (seg::fl_row *)w;
   seg::fl_total *d_totals = (seg::fl_total *)(w + off_tot);
   seg::work_hdr *d_hdr = (seg::work_hdr *)(w + off_hdr);
@@ -1519,37 +1531,24 @@ extern "C" int rgb_segment_flush_device(rgb_ctx *ctx, const rgb_seg_writer *writ
       hipMemsetAsync(d_plan, 0xFF, (size_t)n_entries * sizeof(seg::fl_plan), st) != hipSuccess)
     return RGB_E_HIP;
   (void)hipGetLastError();
-#define SEG_PLAN_LAUNCH(S)                                                                                           \
-  hipLaunchKernelGGL((seg::rgb_flush_plan_kernel<S>), dim3(n_blocks), dim3(seg::THREADS), 0, st, d_writers, n_writers,  \
-                     per_block, (const seg::fl_entry *)d_entries, (seg::u64)data_bytes, max_count, (seg::u64)max_size, \
-                     d_rows, d_plan, d_pc, d_totals)
-  if (n_blocks) {
-    if (width == 8u) SEG_PLAN_LAUNCH(8);
-    else if (width == 16u) SEG_PLAN_LAUNCH(16);
-    else SEG_PLAN_LAUNCH(64);
-  }
-#undef SEG_PLAN_LAUNCH
+  if (n_blocks)
+    seg::with_width(plan_width, [&](auto g) {
+      hipLaunchKernelGGL((seg::rgb_flush_plan_kernel<decltype(g)::value>), dim3(n_blocks), dim3(seg::THREADS), 0, st,
+                         d_writers, n_writers, per_block, (const seg::fl_entry *)d_entries, (seg::u64)data_bytes,
+                         max_count, (seg::u64)max_size, d_rows, d_plan, d_pc, d_totals);
+    });
   hipLaunchKernelGGL(seg::rgb_flush_place_kernel, dim3(n_blocks ? n_blocks : 1u), dim3(seg::THREADS), 0, st, d_writers,
                      n_writers, per_block, n_blocks, (const seg::fl_total *)d_totals, d_rows, d_plan,
                      (const seg::fl_piece *)d_pc, max_count, pieces_cap, (seg::u64)out_bytes, d_hdr, d_pieces,
                      (unsigned char *)d_out, d_result);
   if (n_entries && n_writers) {
-    /* the lane-group width of rgb_segment_build_device */
-    const uint32_t n = n_entries;
-    const uint64_t mean = data_bytes / n;
-#define SEG_FLUSH_LAUNCH(G)                                                                                          \
-  do {                                                                                                               \
-    const seg::u32 per = seg::THREADS / (G);                                                                         \
-    seg::u32 cgrid = (n + per - 1) / per;                                                                            \
-    if (cgrid > seg::GRID_CAP) cgrid = seg::GRID_CAP;                                                                \
-    hipLaunchKernelGGL((seg::rgb_flush_copy_kernel<G>), dim3(cgrid), dim3(seg::THREADS), 0, st,                      \
-                       (const seg::fl_entry *)d_entries, n, (const unsigned char *)d_data,                           \
-                       (const seg::fl_place *)d_plan, (const seg::work_hdr *)d_hdr, flags, (unsigned char *)d_out);  \
-  } while (0)
-    if (mean <= 320u) SEG_FLUSH_LAUNCH(8);
-    else if (mean < 1024u) SEG_FLUSH_LAUNCH(16);
-    else SEG_FLUSH_LAUNCH(64);
-#undef SEG_FLUSH_LAUNCH
+    const seg::u32 width = seg::group_width(data_bytes / n_entries);
+    seg::with_width(width, [&](auto g) {
+      hipLaunchKernelGGL((seg::rgb_flush_copy_kernel<decltype(g)::value>), dim3(seg::entry_grid(n_entries, width)),
+                         dim3(seg::THREADS), 0, st, (const seg::fl_entry *)d_entries, n_entries,
+                         (const unsigned char *)d_data, (const seg::fl_place *)d_plan, (const seg::work_hdr *)d_hdr, flags,
+                         (unsigned char *)d_out);
+    });
   }
   return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
 }
@@ -1567,38 +1566,25 @@ extern "C" int rgb_segment_flush(rgb_ctx *ctx, const rgb_seg_writer *writers, ui
   int rc = rgb_segment_flush_bound(writers, n_writers, n_entries, data_bytes, &bound, &pieces_bound);
   if (rc) return rc;
   for (uint32_t w = 0; w < n_writers; ++w)
-    for (uint32_t i = 0; i < writers[w].entry_n; ++i) {
-      const rgb_seg_entry &e = entries[writers[w].entry_first + i];
-      if (!seg::slice_ok(e.data_offset, e.data_len, data_bytes)) return RGB_E_INVAL;
-    }
+    if (!seg::slices_ok(entries + writers[w].entry_first, writers[w].entry_n, data_bytes)) return RGB_E_INVAL;
   if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
   std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
   seg::stage &s = seg::g_stages[ctx];
   const uint64_t room = out_bytes < bound ? out_bytes : bound;             /* the call never needs more than the bounds */
   const uint32_t rows = pieces_cap < pieces_bound ? pieces_cap : pieces_bound;
-  const size_t need_e = (size_t)n_entries * sizeof(rgb_seg_entry);
-  if (seg::grow(&s.d_entries, &s.cap_e, need_e) || seg::grow(&s.d_data, &s.cap_d, (size_t)data_bytes) ||
-      seg::grow(&s.d_out, &s.cap_out, (size_t)room + 16u) ||
-      seg::grow(&s.d_fl_pieces, &s.cap_fl_pieces, (size_t)rows * sizeof(rgb_seg_piece) + 16u) ||
-      seg::grow(&s.d_fl_result, &s.cap_fl_result, sizeof(rgb_seg_flush_result)))
-    return RGB_E_NOMEM;
   hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
-  if (n_entries && hipMemcpyAsync(s.d_entries, entries, need_e, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  if (data_bytes && hipMemcpyAsync(s.d_data, data, data_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return RGB_E_HIP;
-  rc = rgb_segment_flush_device(ctx, writers, n_writers, s.d_entries, n_entries, s.d_data, data_bytes, max_count, max_size,
-                                flags, s.d_fl_pieces, rows, s.d_out, room, s.d_fl_result, st);
+  if (s.out.reserve((size_t)room + 16u) || s.pieces.reserve((size_t)rows * sizeof(rgb_seg_piece) + 16u) ||
+      s.result.reserve(sizeof(rgb_seg_flush_result)))
+    return RGB_E_NOMEM;
+  if ((rc = seg::stage_in(s.entries, entries, (size_t)n_entries * sizeof(rgb_seg_entry), st)) ||
+      (rc = seg::stage_in(s.data, data, (size_t)data_bytes, st)))
+    return rc;
+  rc = rgb_segment_flush_device(ctx, writers, n_writers, s.entries.p, n_entries, s.data.p, data_bytes, max_count, max_size,
+                                flags, s.pieces.p, rows, s.out.p, room, s.result.p, st);
   if (rc) return rc;
-  rgb_seg_flush_result res;
-  if (hipMemcpyAsync(&res, s.d_fl_result, sizeof res, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-  if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
   /* only the rows and bytes of the answer come back, and only a good answer */
-  if (res.status == RGB_SEG_FLUSH_OK) {
-    if (res.n_pieces && hipMemcpyAsync(pieces, s.d_fl_pieces, (size_t)res.n_pieces * sizeof(rgb_seg_piece),
-                                       hipMemcpyDeviceToHost, st) != hipSuccess)
-      return RGB_E_HIP;
-    if (res.out_bytes && hipMemcpyAsync(out, s.d_out, res.out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
-  }
-  *result = res;
-  return RGB_OK;
+  return seg::fetch_result(result, s.result, RGB_SEG_FLUSH_OK, st, [&](const rgb_seg_flush_result &res) {
+    const int rc_rows = seg::copy_down(pieces, s.pieces, (size_t)res.n_pieces * sizeof(rgb_seg_piece), st);
+    return rc_rows ? rc_rows : seg::copy_down(out, s.out, (size_t)res.out_bytes, st);
+  });
 }

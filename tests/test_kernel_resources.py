@@ -12,6 +12,7 @@ tests/test_gpu_parity.py::test_forced_spill_class_kernel_is_bit_exact).  Scratch
 the cause is unknown -- so the gate stays and covers every group size: the per-tick class kernel and both train kernels
 must compile without scratch for N = 1..8, the kernels rgb_submit launches must not spill for any N, and the class
 kernel must keep its wavefronts per SIMD."""
+import functools
 import os
 import re
 import shutil
@@ -35,6 +36,20 @@ def _parse(stderr):
         if m and cur:
             out[cur][m.group(1).strip()] = int(m.group(2))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def segment_usage():
+    """The remarks for every kernel of rgb_segment.hip: one device-only compile for the tests of the storage path
+    (tests/test_segment.py, test_segment_compact.py, test_segment_flush.py), which each gate their own kernels."""
+    if HIPCC is None:
+        pytest.skip("no hipcc")
+    src = os.path.join(ROOT, "ra_amd", "csrc", "rgb_segment.hip")
+    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-mllvm",
+                        "-disable-machine-licm", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return _parse(r.stderr)
 
 
 @pytest.fixture(scope="module")

@@ -476,15 +476,8 @@ def test_segment_scan_under_sanitizers(tmp_path):
 def test_new_kernels_use_no_scratch():
     """hipcc's resource remarks for gfx950 (no GPU needed), as tests/test_kernel_resources.py reads them: every
     kernel of rgb_segment.hip without scratch or spills, 20 KiB of LDS, at least 7 wavefronts per SIMD."""
-    from test_kernel_resources import HIPCC, _parse
-    if HIPCC is None:
-        pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "ra_amd", "csrc", "rgb_segment.hip")
-    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-mllvm",
-                        "-disable-machine-licm", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage = _parse(r.stderr)
+    from test_kernel_resources import segment_usage
+    usage = segment_usage()
     names = [k for k in usage if "rgb_seg_" in k]
     assert len(names) == 8, names                       # 3 widths x {crc, build}, stream, combine
     for k in names:
