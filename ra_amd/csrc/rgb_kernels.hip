@@ -434,6 +434,64 @@ __device__ __forceinline__ int run_search(const Lane &L, u64 idx, u64 &term) {
   return -1;
 }
 
+/* run_search on a CANONICAL table (PK_CANON_SH) of three and more runs: the starts of the in-memory runs strictly
+ * increase, so "the first run from the new end that starts at or below idx" is the predecessor of idx among them and a
+ * bisection finds it: 1 + ceil(log2(n_runs - 2)) dependent round trips at most where the walk takes n_runs - 2 (a lane
+ * whose idx still lies in run 0 walked the whole table to learn "0", and its wavefront lived as long as it did).
+ * The first round trip asks for the newest in-memory run -- the walk's first probe: "found at once" costs what it did --
+ * and for run 1 together; idx below run 1's start is run 0, which on a canonical table starts at or below first_index:
+ * its pair is read only for a term (WANT_TERM), for the walk cache, or for an idx below first_index (the -1 answer).  What lies between is
+ * halved with one 16-byte load per step, two pairs and one start live.  The walk cache is left as the walk leaves it.
+ * Rows without the bit keep run_search: their starts need not increase and the first match from the new end is the
+ * defined answer. */
+template <bool WANT_TERM, class Lane>
+__device__ __forceinline__ int run_search_canonical(const Lane &L, u64 idx, u64 &term) {
+  const int top = (int)L.n_runs - 3;
+  if (top < 0) return -1;
+  if (Lane::walk_cache && L.wc_k >= 0 && L.wc_k <= top && idx >= L.wc_start && idx < L.wc_next) {
+    term = L.wc_term;
+    return L.wc_k;
+  }
+  ulonglong2 lo = run_pair(L, top);                     /* becomes the newest run known to start at or below idx */
+  const ulonglong2 one = run_pair(L, top > 0 ? 1 : 0);
+#ifdef RGB_PROFILE
+  const_cast<Lane &>(L).prof_nloads += top > 0 ? 4u : 2u;
+#endif
+  u64 upper = L.prs;                                    /* start of run k + 1 */
+  int k = top;
+  if (idx < lo.x) {
+    if (top == 0) return -1;
+    upper = one.x; k = 0;
+    if (idx >= one.x) {
+      int hi = top;                                     /* runs k .. hi - 1 may hold idx; run hi starts at `upper` */
+      upper = lo.x; lo = one; k = 1;
+#pragma unroll 1
+      while (hi - k > 1) {
+        const int mid = (k + hi) >> 1;
+        const ulonglong2 m = run_pair(L, mid);
+#ifdef RGB_PROFILE
+        const_cast<Lane &>(L).prof_nloads += 2u;
+#endif
+        if (idx >= m.x) { lo = m; k = mid; } else { upper = m.x; hi = mid; }
+      }
+    } else if (WANT_TERM || Lane::walk_cache || idx < L.first) {
+      lo = run_pair(L, 0);
+#ifdef RGB_PROFILE
+      const_cast<Lane &>(L).prof_nloads += 2u;
+#endif
+      if (idx < lo.x) return -1;
+    } else {
+      return 0;                                         /* run 0 starts at or below first_index <= idx: no load */
+    }
+  }
+  term = lo.y;
+  if (Lane::walk_cache) {
+    Lane &M = const_cast<Lane &>(L);
+    M.wc_k = k; M.wc_start = lo.x; M.wc_term = lo.y; M.wc_next = upper;
+  }
+  return k;
+}
+
 /* ra_log:fetch_term/2 (src/ra_log.erl:1186-1200): defined only inside the range */
 template <class Lane>
 __device__ __forceinline__ u64 fetch_term(const Lane &L, u64 idx) {
@@ -481,7 +539,7 @@ __device__ __forceinline__ bool quorum_term_gate(u64 pk, unsigned n_runs, u64 ct
 
 /* index of the run holding idx (largest k with start_k <= idx), -1 if none.  Only called
  * before any edit of this message is pending. */
-template <class Lane>
+template <bool BISECT = false, class Lane>
 __device__ __forceinline__ int find_run(const Lane &L, u64 idx) {
   if (L.n_runs == 0) return -1;
   if (idx >= L.lrs) return (int)L.n_runs - 1;
@@ -490,6 +548,8 @@ __device__ __forceinline__ int find_run(const Lane &L, u64 idx) {
 #endif
   if (L.n_runs >= 2 && idx >= L.prs) return (int)L.n_runs - 2;
   u64 term;
+  /* BISECT: the call sites whose walk is from memory and long (log_snapshot_written, truncate_runs_to) */
+  if (BISECT && pk_get(L.pk, PK_CANON_SH, 1)) return run_search_canonical<false>(L, idx, term);
   return run_search(L, idx, term);
 }
 
@@ -780,7 +840,7 @@ __device__ __forceinline__ void push_segment(Lane &L, u64 s, u64 t) {
  * keep_idx); runs starting above it disappear.  keep_term = term_at(keep_idx) if known. */
 template <class Lane>
 __device__ __forceinline__ void truncate_runs_to(Lane &L, u64 keep_idx) {
-  int k = find_run(L, keep_idx);
+  int k = find_run<true>(L, keep_idx);
   if (k < 0) { L.n_runs = 0; return; }
   if ((unsigned)k != L.n_runs - 1) {
     if ((unsigned)k == L.n_runs - 2) { L.lrs = L.prs; L.lrt = L.prt; }
@@ -1125,7 +1185,7 @@ __device__ __forceinline__ bool log_snapshot_written(Lane &L, u64 idx, u64 term)
     L.li = idx; L.lt = term; L.first = idx + 1; L.n_runs = 0;       /* range undefined */
   } else {
     const u64 nf = idx + 1;
-    const int k = find_run(L, nf);
+    const int k = find_run<true>(L, nf);
     u64 *runs = const_cast<u64 *>(L.runs);
     if (k > 0) {
       /* runs k .. n_runs-1 move to the front.  The in-memory ones (k .. n_runs-3) go FOUR AT A TIME -- four independent
@@ -1138,8 +1198,23 @@ __device__ __forceinline__ bool log_snapshot_written(Lane &L, u64 idx, u64 term)
 #ifdef RGB_X_DECLINE_HIST
       atomicAdd(const_cast<u64 *>(L.dbg_hist) + 96 + (n_mem < 0 ? 0 : n_mem > 15 ? 15 : n_mem), 1ull);
 #endif
+      /* The first four -- all there are in 99.9 % of the lanes that move any (profiles/r06_train_decline_hist.txt) --
+       * outside the loop, with CLAMPED source indexes instead of guarded loads: as the loop's first round the guards
+       * and the back edge made the compiler wait for the first pair before it asked for the other three, and for the
+       * previous round's stores before that (two and more round trips where one was meant). */
+      if (n_mem > 0) {
+        const int last = n_mem - 1;
+        const ulonglong2 t0 = ldg16(L.coh, rp + k);
+        const ulonglong2 t1 = ldg16(L.coh, rp + k + (last < 1 ? last : 1));
+        const ulonglong2 t2 = ldg16(L.coh, rp + k + (last < 2 ? last : 2));
+        const ulonglong2 t3 = ldg16(L.coh, rp + k + (last < 3 ? last : 3));
+        ST16(rp, t0);
+        if (last >= 1) ST16(rp + 1, t1);
+        if (last >= 2) ST16(rp + 2, t2);
+        if (last >= 3) ST16(rp + 3, t3);
+      }
 #pragma unroll 1
-      for (int i = 0; i < n_mem; i += 4) {
+      for (int i = 4; i < n_mem; i += 4) {
         ulonglong2 t0 = make_ulonglong2(0, 0), t1 = t0, t2 = t0, t3 = t0;
         t0 = ldg16(L.coh, rp + k + i);
         if (i + 1 < n_mem) t1 = ldg16(L.coh, rp + k + i + 1);
@@ -2138,7 +2213,10 @@ __device__ __forceinline__ void process_message(const rgb_dev &dev, const ulongl
   /* leader-side kinds: fetch the peers row in the same round trip as the hot line (the address
    * only depends on the message); kinds that need it rarely load it lazily */
   L.peers_lds = prepeers; L.peers_swz = swz; L.pdirty = 0;
-  L.runs_lds = preruns;
+  /* (a snapshot_written wavefront never has a staged table -- rgb_tick_slice stages one for the leader-side classes and
+   * for append_entries_rpc only: saying so HERE lets run_pair's LDS branch fold, and two probes that are asked for
+   * together then leave together instead of one behind the other's wait) */
+  L.runs_lds = KIND == RGB_MSG_SNAPSHOT_WRITTEN ? nullptr : preruns;
   /* PL: the class kernel fetched this leader-side message's peers row into LDS with the hot row (128-byte rows:
    * 3..5 members): the clause code reads and writes it there, no register copy.
    * Only the per-tick class kernel (4 wavefronts per SIMD, 128 registers): there the peers row stays in LDS and the
@@ -2197,7 +2275,19 @@ __device__ __forceinline__ void process_message(const rgb_dev &dev, const ulongl
    * servers that are (or just became) followers -- one call site per handler */
   unsigned role1 = role0;
   bool go = true;
-  if (role0 == RGB_ROLE_AWAIT_CONDITION) {
+  if (KIND == RGB_MSG_SNAPSHOT_WRITTEN) {
+    /* Every role's clause for this event is log_snapshot_written and nothing else (handle_leader :745-747, candidate
+     * :1157-1160, pre_vote :1257-1260, await_condition :1946-1949; no role re-processes it); a follower also
+     * acknowledges a last_written that moved (:1457-1474).  Through the role switch below the compiler keeps one inlined
+     * copy of the function PER ROLE, and a wavefront that holds a leader and a follower -- in groups of five nearly every
+     * one -- runs the copies one after the other, each with its own dependent loads of the run table: the class's
+     * clause time was twice what one lane needs.  One call, every lane together. */
+    const bool changed = log_snapshot_written(L, L.a, L.b);
+    const unsigned l4 = (unsigned)pk_get(L.pk, PK_LEADER_SH, 4);
+    if (role0 == RGB_ROLE_FOLLOWER && changed && l4 != SLOT_NONE4) aer_reply(L, L.ct, true, slot4to8(l4));
+    go = false;
+  }
+  if (go && role0 == RGB_ROLE_AWAIT_CONDITION) {
     bool reprocess = false;
     rc = handle_await_condition<N>(L, reprocess, dev.cond + (size_t)L.server * 4);
     go = !rc && reprocess;
