@@ -24,6 +24,15 @@ typedef unsigned long long u64;
 #define WAL_WAVES_PER_BLOCK 4
 #endif
 #define WAL_UNROLL 4            /* 16-byte loads in flight per lane: 4 KiB per wavefront iteration */
+/* a lane's running sums are reduced mod 65521 once they reach this value.  A sum is below it (or below 65521, just
+ * reduced) when a piece is added, and the largest single addition is the (wq a + b) mod 65521 <= 65520 of the loops
+ * (a <= 4080 there; the frame kernel's tail piece adds an unreduced b <= 136 * 255 = 34680 and a <= 15 * 255 = 3825),
+ * so no sum ever exceeds WAL_FOLD_AT - 1 + 65520: that has to fit 32 bits */
+#ifndef WAL_FOLD_AT
+#define WAL_FOLD_AT 0x7FFF0000u
+#endif
+static_assert((unsigned long long)(WAL_FOLD_AT) >= 65521ull && (unsigned long long)(WAL_FOLD_AT) + 65520ull <= 0xFFFFFFFFull,
+              "WAL_FOLD_AT: a reduced sum lies below it, and WAL_FOLD_AT - 1 + 65520 fits a u32");
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ u32 dot4(u32 a, u32 b, u32 c) { return __builtin_amdgcn_udot4(a, b, c, false); }
@@ -108,8 +117,8 @@ __global__ __launch_bounds__(WAL_WAVES_PER_BLOCK * 64) void rgb_wal_adler32_kern
       const u32 wq = (span_q + 2u * ADLER_MOD - (s % ADLER_MOD) - 16u) % ADLER_MOD;
       a_acc += a;                                      /* <= 4080 per chunk */
       b_acc += (wq * a + b) % ADLER_MOD;
-      if (b_acc >= 0x7FFF0000u) b_acc %= ADLER_MOD;
-      if (a_acc >= 0x7FFF0000u) a_acc %= ADLER_MOD;
+      if (b_acc >= WAL_FOLD_AT) b_acc %= ADLER_MOD;
+      if (a_acc >= WAL_FOLD_AT) a_acc %= ADLER_MOD;
     }
   }
   const u32 a_sum = group_sum<GROUP>(a_acc % ADLER_MOD);   /* GROUP * 65520 fits */
@@ -211,8 +220,8 @@ __global__ __launch_bounds__(WAL_WAVES_PER_BLOCK * 64) void rgb_wal_frame_kernel
         chunk_sums(v[k], a, b);
         a_acc += a;
         b_acc += (wq * a + b) % ADLER_MOD;
-        if (b_acc >= 0x7FFF0000u) b_acc %= ADLER_MOD;
-        if (a_acc >= 0x7FFF0000u) a_acc %= ADLER_MOD;
+        if (b_acc >= WAL_FOLD_AT) b_acc %= ADLER_MOD;
+        if (a_acc >= WAL_FOLD_AT) a_acc %= ADLER_MOD;
       }
       wq = wq >= STEP ? wq - STEP : wq + (ADLER_MOD - STEP);
     }

@@ -404,6 +404,77 @@ def test_emu_build_every_phase(emu, small):
     check_build_every_phase(emu, small)
 
 
+# rgb_seg_combine_kernel alone: its rounds behind the first run only with more than 256 partial values, a buffer of more
+# than 16 MiB -- too long for the fibers (the GPU's 64 MiB lengths of check_stream stay).  tests/native exports the
+# kernel on given partial values; the referee is the same polynomial sum in Python.
+
+POLY = 0xEDB88320              # reflected: x^k is bit 31 - k
+
+
+def gf2_mulmod(a: int, b: int) -> int:
+    """a * b mod P over GF(2), both in the reflected representation (zlib's multmodp)"""
+    p, m = 0, 1 << 31
+    while m:
+        if a & m:
+            p ^= b
+        b = (b >> 1) ^ POLY if b & 1 else b >> 1
+        m >>= 1
+    return p
+
+
+def gf2_xpow8(n: int) -> int:
+    """x^(8 n) mod P"""
+    p, sq = 1 << 31, 1 << 23
+    while n:
+        if n & 1:
+            p = gf2_mulmod(sq, p)
+        sq, n = gf2_mulmod(sq, sq), n >> 1
+    return p
+
+
+def raw_crc(m: bytes) -> int:
+    """M(x) x^32 mod P, from zlib: crc(M, init) = ~( ~init x^(8 |M|) ^ raw(M) )  (rgb_segment.hip, "the arithmetic")"""
+    return (~zlib.crc32(m, 0) & 0xFFFFFFFF) ^ gf2_mulmod(0xFFFFFFFF, gf2_xpow8(len(m)))
+
+
+def combine_in_python(partials, xn, start):
+    raw, xblk = 0, gf2_xpow8(STREAM_BLOCK)
+    for p in partials:                                      # Horner: raw = xor_b partials[b] x^(8 STREAM_BLOCK (n - 1 - b))
+        raw = gf2_mulmod(raw, xblk) ^ int(p)
+    return ~(gf2_mulmod(~start & 0xFFFFFFFF, xn) ^ raw) & 0xFFFFFFFF
+
+
+def test_gf2_referee_against_zlib():
+    """The Python arithmetic pinned first: raw(A ++ B) = raw(A) x^(8 |B|) ^ raw(B) and crc(M, init) as the kernel's
+    comment states them, with zlib.crc32 on both sides; and the combine sum itself on a buffer of three blocks."""
+    rng = np.random.default_rng(370)
+    assert gf2_mulmod(1 << 31, 0x12345678) == 0x12345678 and gf2_xpow8(0) == 1 << 31
+    for la, lb in ((0, 5), (1, 1), (17, 4096), (STREAM_BLOCK, 3), (70001, 2 * STREAM_BLOCK)):
+        a, b = rng.bytes(la), rng.bytes(lb)
+        assert raw_crc(a + b) == gf2_mulmod(raw_crc(a), gf2_xpow8(lb)) ^ raw_crc(b), (la, lb)
+        init = int(rng.integers(0, 1 << 32))
+        assert zlib.crc32(b, init) == ~(gf2_mulmod(~init & 0xFFFFFFFF, gf2_xpow8(lb)) ^ raw_crc(b)) & 0xFFFFFFFF
+    m = rng.bytes(2 * STREAM_BLOCK + 77)                    # blocks aligned to the END: the first one is the short one
+    parts = [raw_crc(m[:77]), raw_crc(m[77:77 + STREAM_BLOCK]), raw_crc(m[77 + STREAM_BLOCK:])]
+    assert combine_in_python(parts, gf2_xpow8(len(m)), 0x1234) == zlib.crc32(m, 0x1234)
+
+
+COMBINE_BLOCKS = [1, 2, 255, 256, 257, 511, 512, 513, 1000]
+
+
+@pytest.mark.parametrize("n_blocks", COMBINE_BLOCKS)
+def test_emu_combine_rounds(emu, n_blocks):
+    import ctypes as C
+    fn = emu.engine.lib().emu_seg_combine
+    fn.restype, fn.argtypes = C.c_uint32, [C.c_void_p] + [C.c_uint32] * 5
+    rng = np.random.default_rng(380 + n_blocks)
+    partials = rng.integers(0, 1 << 32, size=n_blocks, dtype=np.uint32)
+    xn, init, held = (int(x) for x in rng.integers(1, 1 << 32, size=3))
+    # the two forms of the starting value: the argument, or what *crc holds (the next gigabyte of one buffer)
+    assert fn(partials.ctypes.data, n_blocks, xn, init, 0, held) == combine_in_python(partials, xn, init)
+    assert fn(partials.ctypes.data, n_blocks, xn, init, 1, held) == combine_in_python(partials, xn, held)
+
+
 def test_emu_refusals(emu):
     check_refusals(emu)
 

@@ -567,6 +567,116 @@ def check_statuses(be):
         assert e.value.code == E_INVAL
 
 
+PAY = 100                       # payload bytes of every record of the precedence cases: `pre` of place p is 100 p
+
+
+def precedence_group(sources, full=None, bad_crc=None, broken=None):
+    """A group whose faults fall on chosen PLACES of the copy order.  sources: per source (places, missing, trunc) --
+    `places` records are selected; `missing`: the live index of that rank is absent from the file, so the record of the
+    next rank takes its place; `trunc`: the record at that place points outside the file.  full = (source, place): the
+    first place with more than max_size payload bytes in front of it.  bad_crc = (source, place): a stored Crc that
+    does not match.  broken = source: its file header is damaged, which info/2 of every file meets before anything is
+    copied, so it wins over every fault of any source.  -> (files, lives, max_size, (status, source, index) worked out
+    from the places alone: the earliest
+    place in copy order, MISSING before TRUNCATED before FULL at one place)."""
+    files, lives, found, front = [], [], [], 0
+    for s, (places, missing, trunc) in enumerate(sources):
+        base = 1000 * s
+        n_live = places + (missing is not None)
+        idxs = [base + i for i in range(1, n_live + 1) if missing is None or i != missing + 1]
+        recs = [R(i, 1 + s, bytes([i % 251]) * PAY) for i in idxs]
+        if trunc is not None:
+            recs[trunc]["off"] = 1 << 40
+        if bad_crc is not None and bad_crc[0] == s:
+            recs[bad_crc[1]]["crc"] = 0x1234567
+        files.append(make_source(recs))
+        lives.append([(base + 1, base + n_live)])
+        here = []
+        if missing is not None:
+            here.append((missing, 0, MISSING, base + missing + 1))
+        if trunc is not None:
+            here.append((trunc, 1, TRUNCATED, idxs[trunc]))
+        if full is not None and full[0] == s:
+            here.append((full[1], 2, FULL, idxs[full[1]]))
+            max_size = front + PAY * full[1] - 1
+            assert max_size >= 0, "nothing can be full at the very first place of a group"
+        if here:
+            found.append((s,) + min(here))
+        front += PAY * places
+    expect = (found[0][3], found[0][0], found[0][4]) if found else None
+    if broken is not None:
+        files[broken] = b"RASX" + files[broken][4:]
+        expect = (BAD_SOURCE, broken, 0)
+    return files, lives, (max_size if full is not None else MAX_SIZE), expect
+
+
+def check_status_precedence(be, width, flags):
+    """MISSING, TRUNCATED and FULL on ONE place of the copy order, and one place or one source apart: the reference
+    meets the missing key first (is_map_key), then reads the payload, then append_raw asks is_full
+    (src/ra_log_segment.erl:819-908), so at one place MISSING wins over TRUNCATED over FULL and otherwise the
+    earlier place wins whatever its kind; a stored Crc that does not match never wins (it is looked at last).
+    Referee: ref_compact, which walks in that order; the expectation worked out from the places has to agree with it."""
+    def run(sources, full=None, bad_crc=None, broken=None, host_form=False, what=""):
+        files, lives, max_size, expect = precedence_group(sources, full, bad_crc, broken)
+        files = pad_to_width(files, sum(len(_expand(l)) for l in lives), width)
+        got = check_group(be, files, lives, max_size=max_size, flags=flags, host_form=host_form, what=what)
+        assert got == expect, f"{what}: the referee says {got}, the places say {expect}"
+
+    front = (1, None, None)                                  # a clean source of one entry: bytes in front of place 0
+    # first, middle and last place of a short selection; both sides of the resolve pass's chunk edge, in the middle of a
+    # selection and as its last place
+    for k, places in ((0, 1), (0, 9), (4, 9), (8, 9), (255, 260), (256, 260), (257, 260), (255, 256), (256, 257)):
+        tag = f"place {k} of {places}"
+        pre, s = ([front], 1) if k == 0 else ([], 0)         # (FULL at place 0 needs bytes of an earlier source)
+        run([(places, k, k)], what=f"(a) {tag}", host_form=k == 4)
+        run(pre + [(places, k, None)], full=(s, k), what=f"(b) {tag}", host_form=k == 4)
+        run(pre + [(places, None, k)], full=(s, k), what=f"(c) {tag}", host_form=k == 4)
+        run(pre + [(places, k, k)], full=(s, k), what=f"(d) {tag}", host_form=k == 4)
+        # (e) one place apart, both orders: the earlier place wins whatever its kind
+        for lo, hi in ((k - 1, k), (k, k + 1)):
+            if lo < 0 or hi >= places:
+                continue
+            for first, second in (("M", "T"), ("T", "M"), ("M", "F"), ("F", "M"), ("T", "F"), ("F", "T")):
+                at = {first: lo, second: hi}
+                if at.get("F") == 0:
+                    continue                                 # (covered by (b)-(d) at k = 0, behind `front`)
+                run([(places, at.get("M"), at.get("T"))], full=(0, at["F"]) if "F" in at else None,
+                    what=f"(e) {first} at {lo}, {second} at {hi} of {places}")
+    # (f) the offending place in the second source; a lower-precedence fault one source later; a higher one earlier
+    clean, k = (40, None, None), 17
+    for name, spec, full in (("a", (60, k, k), None), ("b", (60, k, None), (1, k)), ("c", (60, None, k), (1, k)),
+                             ("d", (60, k, k), (1, k))):
+        run([clean, spec], full=full, what=f"(f) ({name}) in the second source", host_form=True)
+    run([clean, (60, None, k), (30, 0, None)], what="(f) TRUNCATED, MISSING one source later")
+    run([clean, (60, k, None), (30, None, 0)], what="(f) MISSING, TRUNCATED one source later")
+    run([clean, (60, None, k), (30, 0, 0)], full=(1, k), what="(f) TRUNCATED + FULL, everything one source later")
+    run([(40, 39, None), (60, None, None)], full=(1, k), what="(f) FULL, MISSING at the last rank one source earlier")
+    run([(40, None, 39), (60, k, None)], what="(f) MISSING, TRUNCATED at the last place one source earlier")
+    run([(40, None, 0), (60, k, k)], full=(1, k), what="(f) all three, TRUNCATED one source earlier")
+    # BAD_SOURCE first: a damaged header in a LATER source wins over MISSING, TRUNCATED and FULL of an earlier one, and
+    # over a Crc mismatch; the first damaged file is named
+    for name, spec, full in (("a", (60, k, k), None), ("b", (60, k, None), (0, k)), ("c", (60, None, k), (0, k)),
+                             ("d", (60, k, k), (0, k))):
+        run([spec, clean], full=full, broken=1, what=f"BAD_SOURCE behind ({name})", host_form=True)
+    run([clean, (60, None, 0), clean], broken=2, what="BAD_SOURCE two sources behind TRUNCATED at place 0")
+    run([(60, None, None), clean, clean], bad_crc=(0, 3), broken=1, what="BAD_SOURCE behind a Crc mismatch")
+    run([(60, k, None), clean, clean, clean], broken=3, what="BAD_SOURCE in the last source, MISSING in the first")
+    files, lives, _, _ = precedence_group([(60, k, k), clean, clean])
+    files = pad_to_width(files, sum(len(_expand(l)) for l in lives), width)
+    files[1], files[2] = files[1][:7], b"RASG\x00\x03" + files[2][6:]
+    got = check_group(be, files, lives, flags=flags, host_form=False, what="two damaged files: the first is named")
+    assert got == (BAD_SOURCE, 1, 0)
+    # (g) a stored Crc mismatch at an earlier place: with VERIFY it is still not CRC (and without, not looked at)
+    for name, spec, full in (("a", (60, k, k), None), ("b", (60, k, None), (0, k)), ("c", (60, None, k), (0, k)),
+                             ("d", (60, k, k), (0, k))):
+        run([spec], full=full, bad_crc=(0, k - 1), what=f"(g) ({name}) behind a Crc mismatch", host_form=True)
+    # ... and the mismatch alone is CRC with the flag, nothing without
+    files, lives, _, _ = precedence_group([(60, None, None)], bad_crc=(0, k - 1))
+    files = pad_to_width(files, 60, width)
+    got = check_group(be, files, lives, flags=flags, what="(g) the mismatch alone")
+    assert got == (CRC, 0, k) if flags & VERIFY else isinstance(got, bytes)
+
+
 def malformed_descriptors():
     """(name, sources, live pairs, files_bytes, flags) -- each is RGB_E_INVAL"""
     def src(*rows):
@@ -692,6 +802,12 @@ def test_emu_statuses(emu):
     check_statuses(emu)
 
 
+@pytest.mark.parametrize("flags", [0, VERIFY], ids=["plain", "verify"])
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_emu_status_precedence(emu, width, flags):
+    check_status_precedence(emu, width, flags)
+
+
 def test_emu_argument_errors(emu):
     check_argument_errors(emu)
 
@@ -799,6 +915,13 @@ def test_gpu_every_phase(gpu, width, flags):
 @pytest.mark.gpu
 def test_gpu_statuses(gpu):
     check_statuses(gpu)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [0, VERIFY], ids=["plain", "verify"])
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_gpu_status_precedence(gpu, width, flags):
+    check_status_precedence(gpu, width, flags)
 
 
 @pytest.mark.gpu

@@ -9,6 +9,8 @@ import pytest
 
 from ra_amd import abi, engine
 from oracle import oracle as O
+from test_wal_checksum import (EDGE_LENS, FAMILIES, MIB, family_bytes, unfolded_lane_sums,
+                               fold_run)                                 # noqa: F401  (fold_run is a fixture)
 
 
 def header_bytes(trunc: int, id_ref: int, uid: bytes | None) -> bytes:
@@ -18,7 +20,7 @@ def header_bytes(trunc: int, id_ref: int, uid: bytes | None) -> bytes:
     return ((trunc << 23) | id_ref).to_bytes(3, "big") + struct.pack(">H", len(uid)) + uid
 
 
-def make_batch(rng, specs, misalign=True):
+def make_batch(rng, specs, misalign=True, family="random"):
     """specs: [(trunc, id_ref, uid-or-None, index, term, payload_len)] -> (records, data, payloads).
     HeaderData and payload bytes are packed into one data buffer at arbitrary alignment."""
     recs = np.zeros(len(specs), dtype=abi.WAL_RECORD_DTYPE)
@@ -31,7 +33,7 @@ def make_batch(rng, specs, misalign=True):
         chunks.append(h); pos += len(h)
         pad = int(rng.integers(0, 7)) if misalign else 0
         chunks.append(bytes(pad)); pos += pad
-        payload = rng.integers(0, 256, size=ln, dtype=np.uint8).tobytes()
+        payload = family_bytes(rng, family, ln).tobytes()
         payloads.append(payload)
         recs["index"][i], recs["term"][i] = idx, term
         recs["data_offset"][i], recs["data_len"][i] = pos, ln
@@ -62,6 +64,20 @@ def random_specs(rng, n, lens, n_writers=5):
         specs.append((int(rng.integers(0, 2)), w, uids[w] if first else None, idx, int(rng.integers(1, 1 << 30)),
                       int(lens[i])))
     return specs
+
+
+def width_batch(rng, lens, family, width):
+    """Records of `lens` (payloads of `family`) and as many empty records as make rgb_wal_frame_device take `width`
+    lanes per record: 8 up to a mean of 320 bytes, 16 below 1 KiB, else a wavefront.
+    -> (records, data, specs, payloads)"""
+    total = sum(lens)
+    more = {8: total // 300 + 1, 16: total // 900 + 1, 64: 0}[width]       # (a record adds at most 15 bytes of its own)
+    lens = list(lens) + [0] * more
+    specs = random_specs(rng, len(lens), lens, n_writers=7)
+    recs, data, payloads = make_batch(rng, specs, True, family)
+    mean = len(data) // len(recs)
+    assert {8: mean <= 320, 16: 320 < mean < 1024, 64: mean >= 1024}[width], (width, mean)
+    return recs, data, specs, payloads
 
 
 def phase_sweep_batch(rng, lens, src_phases=range(16), dst_phases=range(16)):
@@ -398,6 +414,12 @@ def test_gpu_frame_host_form_then_recovery_round_trip():
     f = bytearray(clean); f[50000:50010] = bytes(10)
     n_ok, status, outcome = recover(bytes(f))
     assert (status, outcome) == (abi.WAL_CORRUPT, "corrupt") and n_ok == (50000 - 5 - 1082) // 1033 + 1
+    # is_last_record/3 at its limit (:994-1010): thirteen bytes behind the failing record decide, twelve are "fewer"
+    f = bytearray(clean); f[-10:] = bytes(10)
+    assert recover(bytes(f) + b"\x01" * 13) == (99, abi.WAL_CORRUPT, "corrupt")
+    assert recover(bytes(f) + bytes(12) + b"\x01") == (99, abi.WAL_CORRUPT, "corrupt")
+    assert recover(bytes(f) + b"\x01" * 12) == (99, abi.WAL_DROPPED_LAST, "dropped_last")
+    assert recover(bytes(f) + bytes(13)) == (99, abi.WAL_DROPPED_LAST, "dropped_last")
     # a stored checksum of 0 means "not used" (:1022-1024): frames written without checksums validate
     body0 = eng.wal_frame(recs, data, total, abi.WAL_NO_CHECKSUMS)
     f = bytearray(abi.WAL_FILE_HEADER + body0.tobytes()); f[1000:1010] = bytes(10)
@@ -471,3 +493,79 @@ def test_gpu_frame_every_source_and_destination_phase(small):
         check_phase_sweep(eng.wal_frame(recs, data, out_bytes).tobytes(), want, out_bytes)
     finally:
         eng.close()
+
+
+# ---- payloads that are not uniformly random, and the accumulator folds -----------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", FAMILIES[1:])
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_gpu_frame_payload_families(width, family):
+    """All 0xFF (the largest sums a length can give), all zero, 0xFF with one zero: all three lane widths."""
+    rng = np.random.default_rng(420 + width + FAMILIES.index(family))
+    recs, data, specs, payloads = width_batch(rng, EDGE_LENS, family, width)
+    total = engine.wal_layout(recs, 0)
+    want = O.wal_frame(recs, data, total)
+    assert want.tobytes() == python_frame(specs, payloads)
+    eng = _open()
+    try:
+        out = eng.wal_frame(recs, data, total)
+    finally:
+        eng.close()
+    bad = np.flatnonzero(out != want)
+    assert len(bad) == 0, f"first differing output byte {bad[0]} of {total}"
+
+
+# (lanes per record, payload bytes, family, the sum that has to pass 2^32)
+FRAME_FOLD_CASES = {"b_8_lanes": (8, 32 * MIB, "random", "b"), "b_16_lanes": (16, 64 * MIB, "random", "b"),
+                    "b_64_lanes": (64, 256 * MIB, "random", "b"), "a_8_lanes": (8, 136 * MIB, "ff", "a")}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(FRAME_FOLD_CASES))
+def test_gpu_frame_folds_at_the_real_threshold(fold_run, case):
+    """As test_wal_checksum.py::test_gpu_adler_folds_at_the_real_threshold, for the framing kernel: one long record
+    (2^18 random pieces per lane for b_acc; 2^20 + 2^16 pieces of 0xFF per lane for a_acc, eight lanes only) among as
+    many empty records as keep the batch's mean payload in the width's band.  The unfolded sums of the lanes are
+    computed first and one has to exceed 2^32.  Referee: zlib.adler32 for the checksum, the 27 bytes in front of the
+    payload by struct.pack, the payload copy at a stride and at both ends, records beside it by python_frame."""
+    torch = fold_run.torch
+    lanes, n_bytes, family, which = FRAME_FOLD_CASES[case]
+    rng = np.random.default_rng(720 + lanes)
+    hdr = header_bytes(0, 3, None)
+    at = 16 + 7                                                # the payload starts 7 bytes into a 16-byte chunk
+    payload = np.frombuffer(rng.bytes(n_bytes), dtype=np.uint8) if family == "random" else family_bytes(rng, family, n_bytes)
+    data = np.concatenate([np.frombuffer(hdr + bytes(at - 3), dtype=np.uint8), payload, np.zeros(16, dtype=np.uint8)])
+    n = {8: len(data) // 320 + 1, 16: len(data) // 1024 + 1, 64: 1}[lanes]
+    mean = len(data) // n
+    assert {8: mean <= 320, 16: 320 < mean < 1024, 64: mean >= 1024}[lanes], (lanes, mean)
+    recs = np.zeros(n, dtype=abi.WAL_RECORD_DTYPE)
+    recs["index"], recs["term"] = np.arange(n) + (1 << 33), 5
+    recs["hdr_offset"], recs["hdr_len"] = 0, 3
+    recs["data_offset"][0], recs["data_len"][0] = at, n_bytes
+    total = engine.wal_layout(recs, 0)
+    assert total == 27 * n + n_bytes
+    a_sums, b_sums = unfolded_lane_sums(payload[:n_bytes & ~15], n_bytes, lanes)
+    top = int((a_sums if which == "a" else b_sums).max())
+    print(f"{case}: largest unfolded {which}_acc of a lane {top} = 2^32 * {top / 2 ** 32:.3f}")
+    assert top > 2 ** 32, "no lane's sum passes 2^32: this input does not reach the fold"
+    want_cs = zlib.adler32(payload, zlib.adler32(struct.pack(">QQ", int(recs["index"][0]), 5)))
+    d_r, d_d = torch.from_numpy(recs.view(np.uint8)).cuda(), torch.from_numpy(data).cuda()
+    d_o = torch.full((total + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+    d_c = torch.zeros(n, dtype=torch.int32, device="cuda")
+    took = fold_run.launch(lambda st: fold_run.eng.wal_frame_device(d_r.data_ptr(), n, d_d.data_ptr(), len(data),
+                                                                    d_o.data_ptr(), total + 64, d_c.data_ptr(), 0, st),
+                           (d_r, d_d, d_o, d_c))
+    print(f"{case}: kernel {took * 1e3:.1f} ms")
+    sums = d_c.cpu().numpy().view(np.uint32)
+    assert int(sums[0]) == want_cs, f"{case}: gpu {int(sums[0]):#x} zlib {want_cs:#x}"
+    got = d_o.cpu().numpy()
+    assert got[:27].tobytes() == hdr + struct.pack(">IIQQ", want_cs, n_bytes, int(recs["index"][0]), 5)
+    body = got[27:27 + n_bytes]
+    assert np.array_equal(body[::4099], payload[::4099]) and np.array_equal(body[:4096], payload[:4096])
+    assert np.array_equal(body[-4096:], payload[-4096:])
+    assert np.all(got[total:] == 0xEE), "wrote behind the records"
+    for i in sorted({1, n // 2, n - 1} - {0} if n > 1 else set()):          # the empty records beside it
+        off = int(recs["out_offset"][i])
+        assert got[off:off + 27].tobytes() == python_frame([(0, 3, None, int(recs["index"][i]), 5, 0)], [b""]), i
+        assert int(sums[i]) == zlib.adler32(struct.pack(">QQ", int(recs["index"][i]), 5))

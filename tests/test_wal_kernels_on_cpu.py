@@ -13,7 +13,9 @@ from ra_amd import abi
 from oracle import oracle as O
 from test_wal_framing import (make_batch as make_records, python_frame, random_specs, scanned_as_tuples,
                                phase_sweep_batch, check_phase_sweep, SWEEP_SMALL, SWEEP_MID, SWEEP_LARGE)
-from test_wal_checksum import make_batch as make_entries, zlib_checksums
+from test_wal_checksum import (make_batch as make_entries, zlib_checksums, width_batch as width_entries, FAMILIES,
+                               EDGE_LENS)
+from test_wal_framing import width_batch as width_records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -134,6 +136,16 @@ def test_recovery_scenarios_of_the_reference(wal):
     assert recover(bytes(f)) == (0, abi.WAL_CORRUPT, "corrupt")
     bad = recs.copy(); bad["out_offset"][5] = bad["out_offset"][4]
     assert wal.wal_frame(bad, data, total)[0] == abi.E_INVAL          # overlapping records
+    # is_last_record/3 at its limit (:994-1010): thirteen bytes behind the failing record decide, twelve are "fewer"
+    f = bytearray(clean); f[-10:] = bytes(10)
+    assert recover(bytes(f) + b"\x01" * 13) == (99, abi.WAL_CORRUPT, "corrupt")
+    assert recover(bytes(f) + bytes(12) + b"\x01") == (99, abi.WAL_CORRUPT, "corrupt")
+    assert recover(bytes(f) + b"\x01" * 12) == (99, abi.WAL_DROPPED_LAST, "dropped_last")
+    assert recover(bytes(f) + bytes(13)) == (99, abi.WAL_DROPPED_LAST, "dropped_last")
+    # a stored checksum of 0 means "not used" (:1022-1024): frames written without checksums validate, damaged or not
+    rc, body0 = wal.wal_frame(recs, data, total, abi.WAL_NO_CHECKSUMS)
+    f = bytearray(abi.WAL_FILE_HEADER + body0.tobytes()); f[1000:1010] = bytes(10)
+    assert rc == 0 and recover(bytes(f)) == (100, abi.WAL_CLEAN, "eof")
 
 
 def test_descriptors_whose_offset_plus_length_wraps_are_refused(wal):
@@ -182,3 +194,106 @@ def test_framing_kernel_at_every_source_and_destination_phase(wal, small):
     rc, out = wal.wal_frame(recs, data, out_bytes)
     assert rc == 0
     check_phase_sweep(out.tobytes(), want, out_bytes)
+
+
+# ---- the accumulator folds (WAL_FOLD_AT of rgb_wal.hip) -------------------------------------------------------
+# At the product's threshold a lane folds after some 65 000 chunks, which the emulation cannot stream in a test's
+# time (the -m gpu tests `..._folds_at_the_real_threshold` do).  What a CPU can check is that a fold, when it happens,
+# is right: the same source built with -DWAL_FOLD_AT=65536u folds b_acc every chunk or two and a_acc every seventeen
+# 0xFF chunks.  Lengths (EDGE_LENS): around the chunk, around zlib's NMAX = 5552 and around the modulus, and 1 MiB.
+
+class WalAlone:
+    """The entry points of a library built from wal_on_cpu.cpp alone (its own dummy context), through ctypes."""
+
+    def __init__(self, path):
+        import ctypes as C
+        L = self.L = C.CDLL(path)
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.emu_wal_ctx.restype = vp
+        L.rgb_wal_adler32.argtypes = [vp, vp, u32, vp, u64, vp]
+        L.rgb_wal_frame.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32]
+        L.rgb_wal_layout.restype = u64
+        L.rgb_wal_layout.argtypes = [vp, u32, u64]
+        self.ctx = L.emu_wal_ctx()
+
+    def wal_adler32(self, entries, data):
+        entries = np.ascontiguousarray(entries, dtype=abi.WAL_ENTRY_DTYPE)
+        out = np.zeros(len(entries), dtype=np.uint32)
+        assert self.L.rgb_wal_adler32(self.ctx, entries.ctypes.data, len(entries), data.ctypes.data, len(data),
+                                      out.ctypes.data) == 0
+        return out
+
+    def wal_frame(self, records, data, out_bytes, flags=0):
+        records = np.ascontiguousarray(records, dtype=abi.WAL_RECORD_DTYPE)
+        out = np.zeros(out_bytes, dtype=np.uint8)
+        rc = self.L.rgb_wal_frame(self.ctx, records.ctypes.data, len(records), data.ctypes.data, len(data),
+                                  out.ctypes.data, out_bytes, flags)
+        return rc, out
+
+    def wal_layout(self, records, base=0):
+        return int(self.L.rgb_wal_layout(records.ctypes.data, len(records), base))
+
+
+@pytest.fixture(scope="module")
+def wal_low_fold(tmp_path_factory):
+    """wal_on_cpu.cpp as a library of its own (its dummy context, the lane emulation inside the unit), folding at 65536."""
+    import shutil
+    import subprocess
+    clang = shutil.which("clang++", path="/opt/rocm/lib/llvm/bin") or shutil.which("clang++")
+    if clang is None:
+        pytest.skip("no clang++ (the emulation build needs __builtin_nontemporal_*)")
+    out = tmp_path_factory.mktemp("wal_low_fold") / "libwal_low_fold.so"
+    nat = os.path.join(ROOT, "tests", "native")
+    cmd = [clang, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-DRGB_EMU_OWN_RUNTIME",
+           "-DWAL_FOLD_AT=65536u", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-Wno-unused-function",
+           "-Wno-unused-variable", "-I", os.path.join(nat, "fake_hip"), "-I", os.path.join(ROOT, "include"),
+           "-o", str(out), os.path.join(nat, "wal_on_cpu.cpp")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return WalAlone(str(out))
+
+
+def check_adler_edges(w, width, family):
+    rng = np.random.default_rng(400 + width + FAMILIES.index(family))
+    entries, data = width_entries(rng, EDGE_LENS, family, width)
+    got = w.wal_adler32(entries, data)
+    want = zlib_checksums(entries, data)
+    bad = np.flatnonzero(got != want)
+    assert len(bad) == 0, f"entry {bad[0]} len {int(entries['data_len'][bad[0]])}: kernel {got[bad[0]]:#x} zlib {want[bad[0]]:#x}"
+
+
+def check_frame_edges(w, width, family):
+    rng = np.random.default_rng(420 + width + FAMILIES.index(family))
+    recs, data, specs, payloads = width_records(rng, EDGE_LENS, family, width)
+    total = w.wal_layout(recs, 0)
+    rc, out = w.wal_frame(recs, data, total)
+    assert rc == 0
+    want = O.wal_frame(recs, data, total)
+    assert want.tobytes() == python_frame(specs, payloads)
+    bad = np.flatnonzero(out != want)
+    assert len(bad) == 0, f"first differing output byte {bad[0]} of {total}"
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("width", [16, 64])
+def test_checksum_kernel_folding_at_65536(wal_low_fold, width, family):
+    check_adler_edges(wal_low_fold, width, family)
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_framing_kernel_folding_at_65536(wal_low_fold, width, family):
+    check_frame_edges(wal_low_fold, width, family)
+
+
+@pytest.mark.parametrize("family", FAMILIES[1:])
+@pytest.mark.parametrize("width", [16, 64])
+def test_checksum_kernel_payload_families(wal, width, family):
+    """The product's threshold, the payloads that are not uniformly random (those: test_checksum_kernel_matches_zlib)."""
+    check_adler_edges(wal, width, family)
+
+
+@pytest.mark.parametrize("family", FAMILIES[1:])
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_framing_kernel_payload_families(wal, width, family):
+    check_frame_edges(wal, width, family)
