@@ -21,6 +21,7 @@
 -export([crc32s/3, crc32_stream/3, segment_build/5, segment_image/4]).
 -export([segment_info/4, segment_compact/6, segment_compact_group/4]).
 -export([segment_flush/7, segment_flush_batch/5]).
+-export([segment_read/5, segment_read_plan/3, segment_term_query_batch/2]).
 -export([encode_msg/3, encode_msgs/1, decode_decision/1, decision_to_effects/3]).
 
 -include_lib("ra/src/ra.hrl").
@@ -235,6 +236,85 @@ flush_pieces_by_writer(_Pieces, WNo, NWriters, _Out1) when WNo >= NWriters -> []
 flush_pieces_by_writer(Pieces, WNo, NWriters, Out1) ->
     {Mine, Rest} = lists:splitwith(fun(P) -> element(1, P) =:= WNo end, Pieces),
     [[Out1(P) || P <- Mine] | flush_pieces_by_writer(Rest, WNo + 1, NWriters, Out1)].
+
+%% reading entries back (src/ra_log_segment.erl:340-359, 375-598, 652-689; src/ra_log_segments.erl:398-622): the read
+%% plans of any number of segment files, of any number of servers, in one call.  SourcesBin = one 32-byte record per
+%% file, little endian: offset:64, n_bytes:64 (the file inside FilesBin), req_first:32, req_n:32 (its indexes inside
+%% ReqBin), 0:64; ReqBin = Idx:64/little per requested index, in the caller's order.  RowsBin = one 32-byte record per
+%% request: idx:64, term:64, data_offset:64 (into OutBin; with Flags 2 into FilesBin; 16#FFFFFFFFFFFFFFFF: no such
+%% entry), data_len:32, crc:32.  ResultsBin = one 32-byte record per file: status:32 (0 ok, 1 missing, 2 truncated,
+%% 3 crc, 4 bad segment), n_read:32, index:64, data_bytes:64, 0:64.  Flags: 1 = validate checksums, 2 = rows only.
+segment_read(_Ctx, _SourcesBin, _FilesBin, _ReqBin, _Flags) -> erlang:nif_error(not_loaded).
+
+%% the descriptors of Plan = [{FileBin, [Idx]}]
+read_plan_bins(Plan) ->
+    {SourcesBin, Files, ReqBin, _, _} =
+        lists:foldl(fun({FileBin, Idxs}, {S, F, Q, Off, First}) ->
+                            Len = byte_size(FileBin),
+                            N = length(Idxs),
+                            {<<S/binary, Off:64/little, Len:64/little, First:32/little, N:32/little, 0:64>>,
+                             [F, FileBin],
+                             << Q/binary, << <<I:64/little>> || I <- Idxs >>/binary >>,
+                             Off + Len, First + N}
+                    end, {<<>>, [], <<>>, 0, 0}, Plan),
+    {SourcesBin, iolist_to_binary(Files), ReqBin}.
+
+%% Plan = [{FileBin, [Idx]}]: per segment file the indexes to read, in any order (read_sparse/4; a fold of From..To is
+%% lists:seq(From, To)).  Opts: validate => boolean() (fold0's validate_checksum, default false), strategy => error |
+%% return (what a fold does with a missing key, default error).  -> {ok, [Answer]}, one per file, in order:
+%% {ok, [{Idx, Term, Bin}]} | {error, {missing_key, Idx}} | {error, {read_error, Idx}} |
+%% {error, {crc_check_failure, Idx}} | {error, bad_segment}; with strategy => return a missing key gives
+%% {ok, Prefix}, the entries in front of it.  One file's error leaves the other files' answers as they are.
+%% The ra_lol search of the segrefs, is_modified/1, the fd LRU, binary_to_term, the mem-table overlay and file I/O
+%% stay in ra_log_segments.
+segment_read_plan(Ctx, Plan, Opts) ->
+    Flags = case maps:get(validate, Opts, false) of true -> 1; false -> 0 end,
+    Strategy = maps:get(strategy, Opts, error),
+    {SourcesBin, FilesBin, ReqBin} = read_plan_bins(Plan),
+    case segment_read(Ctx, SourcesBin, FilesBin, ReqBin, Flags) of
+        {ok, RowsBin, ResultsBin, Out} ->
+            Entries = fun(Rows) ->
+                              [{Idx, Term, binary:part(Out, Off, Len)} ||
+                                  <<Idx:64/little, Term:64/little, Off:64/little, Len:32/little, _Crc:32>> <= Rows]
+                      end,
+            {ok, read_plan_answers(Plan, ResultsBin, RowsBin, 0,
+                                   fun(0, _NRead, _Idx, Rows) -> {ok, Entries(Rows)};
+                                      (1, NRead, _Idx, Rows) when Strategy =:= return ->
+                                           {ok, Entries(binary:part(Rows, 0, 32 * NRead))};
+                                      (1, _NRead, Idx, _Rows) -> {error, {missing_key, Idx}};
+                                      (2, _NRead, Idx, _Rows) -> {error, {read_error, Idx}};
+                                      (3, _NRead, Idx, _Rows) -> {error, {crc_check_failure, Idx}};
+                                      (4, _NRead, _Idx, _Rows) -> {error, bad_segment}
+                                   end)};
+        Error ->
+            Error
+    end.
+
+%% Plan as for segment_read_plan/3 -> {ok, [Answer]}, one per file: {ok, [Term | undefined]} in the order of the
+%% file's indexes (term_query/2) | {error, bad_segment}.  No payload is touched.  One difference from term_query/2:
+%% an index whose record points outside its file (a truncated file) answers `undefined` here, the Term there.
+segment_term_query_batch(Ctx, Plan) ->
+    Undef = 16#FFFFFFFFFFFFFFFF,
+    {SourcesBin, FilesBin, ReqBin} = read_plan_bins(Plan),
+    case segment_read(Ctx, SourcesBin, FilesBin, ReqBin, 2) of
+        {ok, RowsBin, ResultsBin, _Out} ->
+            {ok, read_plan_answers(Plan, ResultsBin, RowsBin, 0,
+                                   fun(4, _NRead, _Idx, _Rows) -> {error, bad_segment};
+                                      (_St, _NRead, _Idx, Rows) ->
+                                           {ok, [case Off of Undef -> undefined; _ -> Term end ||
+                                                    <<_Idx:64/little, Term:64/little, Off:64/little, _:64>> <= Rows]}
+                                   end)};
+        Error ->
+            Error
+    end.
+
+%% the files' slices of RowsBin follow each other in plan order: one pass
+read_plan_answers([], <<>>, _RowsBin, _First, _Answer) -> [];
+read_plan_answers([{_FileBin, Idxs} | Plan], <<St:32/little, NRead:32/little, Idx:64/little, _:128, Results/binary>>,
+                  RowsBin, First, Answer) ->
+    N = length(Idxs),
+    [Answer(St, NRead, Idx, binary:part(RowsBin, 32 * First, 32 * N)) |
+     read_plan_answers(Plan, Results, RowsBin, First + N, Answer)].
 
 %% The bytes of a whole segment file for Entries = [{Idx, Term, Bin}] in the caller's order: what
 %% ra_log_segment:append/4 accumulates in pending_index / pending_data and flush/1 writes

@@ -423,6 +423,109 @@ int rgb_segment_flush(rgb_ctx *ctx, const rgb_seg_writer *writers, uint32_t n_wr
                       uint32_t flags, rgb_seg_piece *pieces, uint32_t pieces_cap, void *out, uint64_t out_bytes,
                       rgb_seg_flush_result *result);
 
+/* ==== reading entries back: read plans, folds and term queries over many segment files in one call =======
+ *
+ * The read half of ra_log_segment: read_sparse/4 and read_sparse_no_checks/4 (src/ra_log_segment.erl:375-598), fold/6,7
+ * and fold0 (:340-359, :661-689), term_query/2 (:652-659), driven over many files by ra_log_segments:exec_read_plan/6,
+ * segment_sparse_read, segment_fold and segment_term_query (src/ra_log_segments.erl:398-622).  One call reads any number
+ * of segment files ("sources", of any number of groups): for every requested index one rgb_seg_entry row
+ * (Idx, Term, where the payload is, Length, the stored Crc), the payloads packed back to back in request order.
+ *
+ * All sources lie in ONE files buffer, all requests in ONE flat list `req` of indexes, each source owning a slice of
+ * it, in the caller's order: ascending, descending, repeated -- whatever a read_sparse index list may be; a fold of
+ * From..To is the caller's expansion of that range.  `sources` and `req` are HOST arrays in both forms: validated on
+ * the host and staged by the library.  Slices ascend by req_first and are disjoint; requests that no slice names are
+ * ignored and their rows are not written.  RGB_E_INVAL, nothing enqueued: a slice outside n_req, slices not ascending
+ * or not disjoint, a source outside files_bytes, unknown flags, VERIFY together with NO_DATA, more than
+ * RGB_SEG_READ_MAX_SOURCES sources.  n_sources == 0 and n_req == 0 are legal.
+ *
+ * Lookup is in the map of parse_index_data_loop (:1057-1075), as in "major compaction" above: the walk ends at the
+ * first all-zero record, at MaxCount records or where the file ends inside the index region; a backwards step trims
+ * every greater key; an equal Idx overwrites -- the effective records.  The reference's binary index mode (:411-572)
+ * is defined only for files whose records ascend and gives the same answers there.  Version 1 and 2 are served.
+ *
+ * Rows are independent; row r answers request r.
+ *   good       index and term the record's, data_len its Length, crc the stored Crc, data_offset where the payload
+ *              starts in `out` (with RGB_SEG_READ_NO_DATA: in the files buffer, source.offset + DataOffset); never
+ *              RGB_UNDEF
+ *   MISSING    the index is not in the map (exit({missing_key, Idx}); not_found in fold0 and term_query)
+ *   TRUNCATED  the record's payload lies outside its file: DataOffset > n_bytes or Length > n_bytes - DataOffset
+ *              (read_error, unexpected_eof, the short pread)
+ *              -- with NO_DATA too, where the reference's term_query/2, which reads the index only, answers the Term
+ * MISSING and TRUNCATED rows are {index = the requested one, term = 0, data_offset = RGB_UNDEF, data_len = 0, crc = 0}
+ * and take no bytes of `out`; the later rows of the source are still looked up and delivered.
+ *
+ * The per-source result reports the first bad row of the slice in request order: its kind, its index and n_read, its
+ * position in the slice (a fold with the `return` strategy takes the first n_read rows; with `error` the caller
+ * crashes that server).  data_bytes counts the payloads of all good rows of the slice (0 with NO_DATA).
+ *
+ * RGB_SEG_READ_VERIFY: the CRC-32 of every copied payload is computed in the read that copies it and compared with
+ * the stored Crc; a stored Crc of 0 is always good (validate_checksum/2, :1245-1248).  A mismatching row is still
+ * delivered.  A source without a MISSING or TRUNCATED row and with a mismatch gets the status CRC, index and n_read
+ * from the first mismatch in request order: MISSING and TRUNCATED win over CRC.  Without the flag no table is loaded
+ * and no CRC computed (read_sparse does not validate).
+ *
+ * BAD_SOURCE: bad magic, fewer than 8 bytes, Version 0 or > 2.  n_read = 0, index = 0, every row of the slice is a
+ * MISSING row.  Per source in BOTH forms (unlike compact's host-buffer form): a batch across groups survives one bad
+ * file.
+ *
+ * SPACE: out_bytes < the bytes needed: total.status = SPACE, total.out_bytes = needed, `out` is not touched, rows and
+ * results are written exactly as they would be, except that CRC is never reported (nothing was copied).  out = NULL,
+ * out_bytes = 0 is therefore the sizing call.  With NO_DATA nothing is needed and SPACE never occurs.
+ *
+ * Only a file's own bytes are read, only the rows in [0, n_req) that slices name and the first total.out_bytes bytes of
+ * `out` are written; d_files and d_out may have any alignment, d_rows, d_results and d_total are 8-byte aligned.  The
+ * scratch lives in the context (released by rgb_close): one read call per context at a time.  Its size: 44 bytes per
+ * source, 32 bytes per request (none with NO_DATA) and, for the tables of effective records, 4 bytes for every record a
+ * source could hold -- min(65535, (n_bytes - 8) / 28) per source, about a seventh of the sources' bytes -- reserved
+ * whether or not a source turns out to need its table.
+ *
+ * ra_lol search of the segrefs, is_modified/1, the fd LRU, binary_to_term, the mem-table overlay and file I/O stay with
+ * the caller. */
+typedef struct rgb_seg_read_source {   /* 32 bytes, the layout of rgb_seg_source */
+  uint64_t offset, n_bytes;            /* the file = files[offset .. offset + n_bytes) */
+  uint32_t req_first, req_n;           /* its requests = req[req_first .. + req_n), in the caller's order */
+  uint64_t _pad;
+} rgb_seg_read_source;
+
+typedef struct rgb_seg_read_result {   /* 32 bytes, one per source */
+  uint32_t status;                     /* RGB_SEG_READ_* of the first bad row in request order */
+  uint32_t n_read;                     /* leading good rows of the slice (== req_n when OK) */
+  uint64_t index;                      /* the index the status is about */
+  uint64_t data_bytes;                 /* payload bytes this source contributes to out */
+  uint64_t _pad;
+} rgb_seg_read_result;
+
+typedef struct rgb_seg_read_total {    /* 16 bytes, one per call */
+  uint32_t status;                     /* RGB_SEG_READ_OK or RGB_SEG_READ_SPACE */
+  uint32_t n_bad;                      /* sources whose status is not OK */
+  uint64_t out_bytes;                  /* OK: bytes of out written; SPACE: bytes needed */
+} rgb_seg_read_total;
+
+#define RGB_SEG_READ_OK         0u
+#define RGB_SEG_READ_MISSING    1u
+#define RGB_SEG_READ_TRUNCATED  2u
+#define RGB_SEG_READ_CRC        3u
+#define RGB_SEG_READ_BAD_SOURCE 4u
+#define RGB_SEG_READ_SPACE      5u   /* rgb_seg_read_total only */
+
+#define RGB_SEG_READ_VERIFY      1u  /* flag: fold0's validate_checksum */
+#define RGB_SEG_READ_NO_DATA     2u  /* flag: rows only (term_query); out may be NULL */
+#define RGB_SEG_READ_MAX_SOURCES 65536u
+
+/* d_rows: n_req rgb_seg_entry rows, d_results: n_sources rgb_seg_read_result rows, *d_total: one rgb_seg_read_total,
+ * all in device memory.  The rows and d_out of a read can be handed unchanged to rgb_crc32_device,
+ * rgb_segment_build_device or rgb_segment_flush_device.  Three launches (two with NO_DATA, four with VERIFY) on
+ * `stream` (NULL = the context's stream), no synchronisation. */
+int rgb_segment_read_device(rgb_ctx *ctx, const rgb_seg_read_source *sources, uint32_t n_sources, const void *d_files,
+                            uint64_t files_bytes, const uint64_t *req, uint32_t n_req, uint32_t flags, void *d_rows,
+                            void *d_out, uint64_t out_bytes, void *d_results, void *d_total, void *stream);
+/* Host-buffer form: synchronises.  `results` and `total` are always written, the named rows too; `out` (its first
+ * total.out_bytes bytes) only when total.status is OK. */
+int rgb_segment_read(rgb_ctx *ctx, const rgb_seg_read_source *sources, uint32_t n_sources, const void *files,
+                     uint64_t files_bytes, const uint64_t *req, uint32_t n_req, uint32_t flags, rgb_seg_entry *rows,
+                     void *out, uint64_t out_bytes, rgb_seg_read_result *results, rgb_seg_read_total *total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,14 @@ SEG_FLUSH_RESULT_DTYPE = np.dtype([("status", u32), ("n_pieces", u32), ("out_byt
                                    ("entry", u32), ("_pad", u64)])
 assert (SEG_WRITER_DTYPE.itemsize, SEG_PIECE_DTYPE.itemsize, SEG_FLUSH_RESULT_DTYPE.itemsize) == (48, 80, 32)
 SEG_FLUSH_OK, SEG_FLUSH_SPACE, SEG_FLUSH_ENTRY = range(3)
+# reading entries back (same header): one source of a call, its result, the call's total; the rows are SEG_ENTRY_DTYPE
+SEG_READ_SOURCE_DTYPE = np.dtype([("offset", u64), ("n_bytes", u64), ("req_first", u32), ("req_n", u32), ("_pad", u64)])
+SEG_READ_RESULT_DTYPE = np.dtype([("status", u32), ("n_read", u32), ("index", u64), ("data_bytes", u64), ("_pad", u64)])
+SEG_READ_TOTAL_DTYPE = np.dtype([("status", u32), ("n_bad", u32), ("out_bytes", u64)])
+assert (SEG_READ_SOURCE_DTYPE.itemsize, SEG_READ_RESULT_DTYPE.itemsize, SEG_READ_TOTAL_DTYPE.itemsize) == (32, 32, 16)
+(SEG_READ_OK, SEG_READ_MISSING, SEG_READ_TRUNCATED, SEG_READ_CRC, SEG_READ_BAD_SOURCE, SEG_READ_SPACE) = range(6)
+SEG_READ_VERIFY, SEG_READ_NO_DATA = 1, 2
+SEG_READ_MAX_SOURCES = 65536
 
 # rgb_view (ABI v9, rgb_collect_view): pointers into the pinned slot the device wrote
 VIEW_DTYPE = np.dtype([("decisions", "<u8"), ("rpcs", "<u8"), ("tick", "<u8"), ("n", "<u4"), ("n_rpcs", "<u4"),

@@ -828,6 +828,50 @@ static ERL_NIF_TERM nif_segment_flush(ErlNifEnv *env, int argc, const ERL_NIF_TE
   return enif_make_tuple3(env, enif_make_atom(env, "ok"), enif_make_binary(env, &pieces), enif_make_binary(env, &out));
 }
 
+/* segment_read(Ctx, SourcesBin, FilesBin, ReqBin, Flags) -> {ok, RowsBin, ResultsBin, OutBin} | {error, _}: a read plan
+ * over many segment files in one call -- ra_log_segment:read_sparse/4, fold/6 and term_query/2 (src/ra_log_segment.erl:
+ * 340-359, 375-598, 652-689) as ra_log_segments:exec_read_plan/6 drives them (src/ra_log_segments.erl:398-622).
+ * SourcesBin = S rgb_seg_read_source records, ReqBin = the requested indexes as native 64-bit unsigned integers;
+ * RowsBin = one rgb_seg_entry per request (data_offset into OutBin; with Flags 2 into FilesBin), ResultsBin = one
+ * rgb_seg_read_result per source, OutBin = the payloads back to back in request order.  Flags: 1 = validate every
+ * payload against its stored Crc, 2 = rows only.  OutBin is sized by a sizing call (out = NULL). */
+static ERL_NIF_TERM nif_segment_read(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary s, f, q, rows, results, out; unsigned flags;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &s) || !enif_inspect_binary(env, argv[2], &f) ||
+      !enif_inspect_binary(env, argv[3], &q) || !enif_get_uint(env, argv[4], &flags) ||
+      s.size % sizeof(rgb_seg_read_source) != 0 || q.size % 8u != 0 ||
+      s.size / sizeof(rgb_seg_read_source) > RGB_SEG_READ_MAX_SOURCES || q.size / 8u > 0xFFFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(s.size / sizeof(rgb_seg_read_source)), n_req = (uint32_t)(q.size / 8u);
+  const rgb_seg_read_source *sources = (const rgb_seg_read_source *)s.data;
+  const uint64_t *req = (const uint64_t *)q.data;
+  if (!enif_alloc_binary((size_t)(n_req ? n_req : 1) * sizeof(rgb_seg_entry), &rows)) return mk_error(env, c, RGB_E_NOMEM);
+  if (!enif_alloc_binary((size_t)(n ? n : 1) * sizeof(rgb_seg_read_result), &results)) {
+    enif_release_binary(&rows);
+    return mk_error(env, c, RGB_E_NOMEM);
+  }
+  memset(rows.data, 0, rows.size);                      /* requests that no slice names: rows of zeros */
+  rgb_seg_read_total total;
+  int rc = rgb_segment_read(c->ctx, sources, n, f.data, f.size, req, n_req, flags, (rgb_seg_entry *)rows.data, NULL, 0,
+                            (rgb_seg_read_result *)results.data, &total);
+  const uint64_t needed = rc ? 0 : total.out_bytes;
+  if (!rc && !enif_alloc_binary((size_t)(needed ? needed : 1), &out)) rc = RGB_E_NOMEM;
+  if (rc) { enif_release_binary(&rows); enif_release_binary(&results); return mk_error(env, c, rc); }
+  if (total.status == RGB_SEG_READ_SPACE)
+    rc = rgb_segment_read(c->ctx, sources, n, f.data, f.size, req, n_req, flags, (rgb_seg_entry *)rows.data, out.data,
+                          needed, (rgb_seg_read_result *)results.data, &total);
+  if (rc || total.status != RGB_SEG_READ_OK) {          /* (the second call has what the first one asked for) */
+    enif_release_binary(&rows); enif_release_binary(&results); enif_release_binary(&out);
+    return mk_error(env, c, rc ? rc : RGB_E_INVAL);
+  }
+  enif_realloc_binary(&rows, (size_t)n_req * sizeof(rgb_seg_entry));
+  enif_realloc_binary(&results, (size_t)n * sizeof(rgb_seg_read_result));
+  enif_realloc_binary(&out, (size_t)total.out_bytes);
+  return enif_make_tuple4(env, enif_make_atom(env, "ok"), enif_make_binary(env, &rows), enif_make_binary(env, &results),
+                          enif_make_binary(env, &out));
+}
+
 static ErlNifFunc nif_funcs[] = {
   {"open", 4, nif_open, 0},
   {"register_groups", 3, nif_register_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
@@ -857,6 +901,7 @@ static ErlNifFunc nif_funcs[] = {
   {"segment_info", 4, nif_segment_info, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_compact", 6, nif_segment_compact, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_flush", 7, nif_segment_flush, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_read", 5, nif_segment_read, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(ra_gpu_batch, nif_funcs, on_load, NULL, NULL, NULL)

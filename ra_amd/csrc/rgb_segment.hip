@@ -399,60 +399,43 @@ __device__ __forceinline__ bool live_find(const u64 *live, u32 first, u32 n, u64
   return idx <= live[2 * (u64)*which + 1u];
 }
 
-__global__ __launch_bounds__(THREADS) void rgb_compact_resolve_kernel(
-    const src_desc *__restrict__ srcs, const unsigned char *__restrict__ files, const u64 *__restrict__ live,
-    const u32 *__restrict__ rank, u32 all_live, void *infos_v, src_done *__restrict__ done, plan_rec *__restrict__ plan) {
-  __shared__ u64 s_wide[THREADS];                       /* scan buffer: suffix min of Idx, prefix sum of bytes */
-  __shared__ u32 s_cnt[THREADS];                        /* scan buffer: prefix count */
-  __shared__ u32 s_bits[CMP_MAX_RECORDS / 32];          /* record j is effective */
-  __shared__ u32 s_first_zero, s_eff, s_miss_k, s_trunc_k;
-  __shared__ u64 s_live_size;
-  const u32 tid = threadIdx.x, s = blockIdx.x;
-  const src_desc sd = srcs[s];
-  const unsigned char *f = files + sd.offset;
-  rgb_seg_info *info = infos_v ? reinterpret_cast<rgb_seg_info *>(infos_v) + s : nullptr;
-
-  /* read_header/1 (:1124-1138) */
-  u32 version = 0, max_count = 0;
-  if (sd.n_bytes >= RGB_SEG_HEADER_BYTES && f[0] == 'R' && f[1] == 'A' && f[2] == 'S' && f[3] == 'G') {
-    version = ((u32)f[4] << 8) | f[5];
-    max_count = ((u32)f[6] << 8) | f[7];
+/* read_header/1 (:1124-1138): version 0 = not a segment file this unit serves */
+__device__ __forceinline__ void read_header(const unsigned char *f, u64 n_bytes, u32 *version, u32 *max_count) {
+  *version = 0; *max_count = 0;
+  if (n_bytes >= RGB_SEG_HEADER_BYTES && f[0] == 'R' && f[1] == 'A' && f[2] == 'S' && f[3] == 'G') {
+    *version = ((u32)f[4] << 8) | f[5];
+    *max_count = ((u32)f[6] << 8) | f[7];
   }
-  if (version < 1u || version > RGB_SEG_VERSION) {      /* the same for every lane */
-    if (tid == 0u) {
-      if (info) { rgb_seg_info z{}; z.status = RGB_SEG_COMPACT_BAD_SOURCE; *info = z; }
-      if (done) { src_done d{}; d.miss_k = d.trunc_k = NONE32; d.bad = 1u; done[s] = d; }
-    }
-    return;
-  }
-  const bool v2 = version == 2u;
-  const u32 rec_bytes = v2 ? RGB_SEG_RECORD_BYTES : RGB_SEG_RECORD_BYTES_V1;
-  const u64 data_start = (u64)RGB_SEG_HEADER_BYTES + (u64)rec_bytes * max_count;
-  const u64 fit = (sd.n_bytes - RGB_SEG_HEADER_BYTES) / rec_bytes;            /* whole records inside the file */
-  const u32 n_fit = fit < max_count ? (u32)fit : max_count;
-  const unsigned char *index = f + RGB_SEG_HEADER_BYTES;
+}
 
-  /* pass A: where the walk ends -- the first all-zero record */
-  if (tid == 0u) { s_first_zero = n_fit; s_eff = 0u; s_miss_k = NONE32; s_trunc_k = NONE32; s_live_size = 0ull; }
+/* The index walk of one source by its workgroup (every lane comes here), for the resolve passes of compaction and of
+ * the reads.  Pass A: where the walk ends -- the first all-zero record among the n_fit whole records inside the file.
+ * Pass B, last chunk first: record j is effective iff Idx_j < min Idx of every later record (the last one always is)
+ * -- a reverse exclusive min-scan, `carry` the minimum of the chunks already seen.  Leaves the effective bitmap in
+ * s_bits, their number in *s_eff (both valid after the last barrier in here), the smallest Idx walked in *min_idx;
+ * returns the records walked.  each(r) sees every walked record once, on its own lane.  The caller has a barrier
+ * between its own use of the LDS arrays and this call. */
+template <class F>
+__device__ __forceinline__ u32 walk_effective(const unsigned char *index, u32 rec_bytes, bool v2, u32 n_fit, u64 *s_wide,
+                                              u32 *s_bits, u32 *s_first_zero, u32 *s_eff, u64 *min_idx, F &&each) {
+  const u32 tid = threadIdx.x;
+  if (tid == 0u) { *s_first_zero = n_fit; *s_eff = 0u; }
   for (u32 i = tid; i < CMP_MAX_RECORDS / 32; i += THREADS) s_bits[i] = 0u;
   __syncthreads();
   for (u32 base = 0; base < n_fit; base += THREADS) {
     const u32 j = base + tid;
     if (j < n_fit) {
       const idx_rec r = decode_rec(index + (u64)rec_bytes * j, v2);
-      if ((r.idx | r.term | r.off | r.len | r.crc) == 0ull) atomic_min(&s_first_zero, j);
+      if ((r.idx | r.term | r.off | r.len | r.crc) == 0ull) atomic_min(s_first_zero, j);
     }
     __syncthreads();
-    const u32 z = s_first_zero;
+    const u32 z = *s_first_zero;
     __syncthreads();
     if (z != n_fit) break;
   }
-  const u32 n_walk = s_first_zero;
+  const u32 n_walk = *s_first_zero;
   const u32 n_chunks = (n_walk + THREADS - 1u) / THREADS;
-
-  /* pass B, last chunk first: record j is effective iff Idx_j < min Idx of every later record (the last one always
-   * is) -- a reverse exclusive min-scan, `carry` the minimum of the chunks already seen */
-  u64 carry = NONE64, my_live = 0;
+  u64 carry = NONE64;
   for (u32 c = n_chunks; c-- > 0u;) {
     const u32 j = c * THREADS + tid;
     const bool valid = j < n_walk;
@@ -472,13 +455,54 @@ __global__ __launch_bounds__(THREADS) void rgb_compact_resolve_kernel(
     const u64 chunk_min = s_wide[0];
     if (valid && (j == n_walk - 1u || r.idx < later)) {
       atomicOr(&s_bits[j >> 5], 1u << (j & 31u));
-      atomicAdd(&s_eff, 1u);
+      atomicAdd(s_eff, 1u);
     }
-    u32 which;
-    if (valid && (all_live || live_find(live, sd.live_first, sd.live_n, r.idx, &which))) my_live += r.len;
+    if (valid) each(r);
     if (chunk_min < carry) carry = chunk_min;
     __syncthreads();
   }
+  *min_idx = carry;
+  return n_walk;
+}
+
+__global__ __launch_bounds__(THREADS) void rgb_compact_resolve_kernel(
+    const src_desc *__restrict__ srcs, const unsigned char *__restrict__ files, const u64 *__restrict__ live,
+    const u32 *__restrict__ rank, u32 all_live, void *infos_v, src_done *__restrict__ done, plan_rec *__restrict__ plan) {
+  __shared__ u64 s_wide[THREADS];                       /* scan buffer: suffix min of Idx, prefix sum of bytes */
+  __shared__ u32 s_cnt[THREADS];                        /* scan buffer: prefix count */
+  __shared__ u32 s_bits[CMP_MAX_RECORDS / 32];          /* record j is effective */
+  __shared__ u32 s_first_zero, s_eff, s_miss_k, s_trunc_k;
+  __shared__ u64 s_live_size;
+  const u32 tid = threadIdx.x, s = blockIdx.x;
+  const src_desc sd = srcs[s];
+  const unsigned char *f = files + sd.offset;
+  rgb_seg_info *info = infos_v ? reinterpret_cast<rgb_seg_info *>(infos_v) + s : nullptr;
+
+  u32 version, max_count;
+  read_header(f, sd.n_bytes, &version, &max_count);
+  if (version < 1u || version > RGB_SEG_VERSION) {      /* the same for every lane */
+    if (tid == 0u) {
+      if (info) { rgb_seg_info z{}; z.status = RGB_SEG_COMPACT_BAD_SOURCE; *info = z; }
+      if (done) { src_done d{}; d.miss_k = d.trunc_k = NONE32; d.bad = 1u; done[s] = d; }
+    }
+    return;
+  }
+  const bool v2 = version == 2u;
+  const u32 rec_bytes = v2 ? RGB_SEG_RECORD_BYTES : RGB_SEG_RECORD_BYTES_V1;
+  const u64 data_start = (u64)RGB_SEG_HEADER_BYTES + (u64)rec_bytes * max_count;
+  const u64 fit = (sd.n_bytes - RGB_SEG_HEADER_BYTES) / rec_bytes;            /* whole records inside the file */
+  const u32 n_fit = fit < max_count ? (u32)fit : max_count;
+  const unsigned char *index = f + RGB_SEG_HEADER_BYTES;
+
+  /* passes A and B: the walk, the effective records, and live_size over every walked record */
+  if (tid == 0u) { s_miss_k = NONE32; s_trunc_k = NONE32; s_live_size = 0ull; }
+  u64 carry, my_live = 0;
+  const u32 n_walk = walk_effective(index, rec_bytes, v2, n_fit, s_wide, s_bits, &s_first_zero, &s_eff, &carry,
+                                    [&](const idx_rec &r) {
+    u32 which;
+    if (all_live || live_find(live, sd.live_first, sd.live_n, r.idx, &which)) my_live += r.len;
+  });
+  const u32 n_chunks = (n_walk + THREADS - 1u) / THREADS;
   if (my_live) atomicAdd(&s_live_size, (unsigned long long)my_live);
   __syncthreads();
 
@@ -657,6 +681,273 @@ __global__ void rgb_compact_finish_kernel(const plan_rec *__restrict__ plan, con
   res.source = plan[hdr->crc_fail].src;
   res.index = plan[hdr->crc_fail].idx;
   __builtin_memcpy(result_v, &res, sizeof res);
+}
+
+/* ---- reading entries back (include/ra_gpu_wal.h, "reading entries back") -----------------------------------
+ * Passes, each its own launch, so that no workgroup ever waits for another:
+ *   resolve  one workgroup per source: the walk and the effective records as in compaction (walk_effective), the
+ *            effective records' numbers as one ascending table in scratch (their Idx ascend with them; a source whose
+ *            records are all effective needs none: the record number IS the place), then the source's requests in steps
+ *            of THREADS: a binary search each, the row, the bytes in front of it within the slice (LDS scan, carried
+ *            from step to step), the first MISSING and the first TRUNCATED position
+ *   place    one workgroup: the sources' first bytes in `out` (a scan in steps of THREADS, carried from step to step),
+ *            their result rows, the total and SPACE
+ *   copy     GROUP lanes per good row: the final data_offset and, unless the status is SPACE, the payload -- with
+ *            VERIFY its CRC in the same read, and per source the first position whose CRC does not match
+ *   finish   (VERIFY) one workgroup: those positions into CRC statuses
+ * With NO_DATA the rows are final after resolve, and copy and finish are not launched.
+ * The kernels' parameter types are the unit's own (see "major compaction" above). */
+struct rd_src { u64 offset, n_bytes; u32 req_first, req_n; u64 tab_base; };                 /* staged from the host */
+struct rd_done { u64 bytes, bad_idx; u32 bad_k, kind; u64 _pad; };                          /* resolve -> place */
+struct alignas(16) rd_plan { u64 src_off, pre; u32 src, pos, len, crc; };                   /* resolve -> copy, per request */
+struct rd_row { u64 idx, term, off; u32 len, crc; };
+static_assert(sizeof(rd_src) == sizeof(rgb_seg_read_source) && sizeof(rd_done) == 32 && sizeof(rd_plan) == 32, "");
+static_assert(sizeof(rd_row) == sizeof(rgb_seg_entry) && sizeof(rgb_seg_read_result) == 32 && sizeof(rgb_seg_read_total) == 16, "");
+
+__device__ __forceinline__ rd_row missing_row(u64 idx) {
+  rd_row w;
+  w.idx = idx; w.term = 0ull; w.off = RGB_UNDEF; w.len = 0u; w.crc = 0u;
+  return w;
+}
+
+/* the plan record of a row that has nothing to copy */
+__device__ __forceinline__ rd_plan no_plan() {
+  rd_plan p;
+  p.src_off = p.pre = 0ull; p.src = NONE32; p.pos = p.len = p.crc = 0u;
+  return p;
+}
+
+__global__ __launch_bounds__(THREADS) void rgb_read_resolve_kernel(
+    const rd_src *__restrict__ srcs, const unsigned char *__restrict__ files, const u64 *__restrict__ req, u32 no_data,
+    u32 *tab, void *rows_v, rd_plan *__restrict__ plan, rd_done *__restrict__ done) {
+  __shared__ u64 s_wide[THREADS];                       /* scan buffer: suffix min of Idx, prefix sum of bytes */
+  __shared__ u32 s_cnt[THREADS];                        /* scan buffer: prefix count */
+  __shared__ u32 s_bits[CMP_MAX_RECORDS / 32];          /* record j is effective */
+  __shared__ u32 s_first_zero, s_eff, s_miss_k, s_trunc_k;
+  const u32 tid = threadIdx.x, s = blockIdx.x;
+  const rd_src sd = srcs[s];
+  const unsigned char *f = files + sd.offset;
+  const u64 *asked = req + sd.req_first;
+  rd_row *rows = reinterpret_cast<rd_row *>(rows_v) + sd.req_first;
+
+  u32 version, max_count;
+  read_header(f, sd.n_bytes, &version, &max_count);
+  if (version < 1u || version > RGB_SEG_VERSION) {      /* the same for every lane */
+    for (u32 k = tid; k < sd.req_n; k += THREADS) {
+      rows[k] = missing_row(asked[k]);
+      if (!no_data) plan[sd.req_first + k] = no_plan();
+    }
+    if (tid == 0u) { rd_done d{}; d.kind = RGB_SEG_READ_BAD_SOURCE; done[s] = d; }
+    return;
+  }
+  const bool v2 = version == 2u;
+  const u32 rec_bytes = v2 ? RGB_SEG_RECORD_BYTES : RGB_SEG_RECORD_BYTES_V1;
+  const u64 fit = (sd.n_bytes - RGB_SEG_HEADER_BYTES) / rec_bytes;            /* whole records inside the file */
+  const u32 n_fit = fit < max_count ? (u32)fit : max_count;
+  const unsigned char *index = f + RGB_SEG_HEADER_BYTES;
+
+  if (tid == 0u) { s_miss_k = NONE32; s_trunc_k = NONE32; }
+  u64 min_idx;
+  const u32 n_walk = walk_effective(index, rec_bytes, v2, n_fit, s_wide, s_bits, &s_first_zero, &s_eff, &min_idx,
+                                    [](const idx_rec &) {});
+  const u32 n_chunks = (n_walk + THREADS - 1u) / THREADS;
+  const u32 n_eff = s_eff;
+  const bool dense = n_eff == n_walk;                   /* every record effective: place k is record k */
+  u32 *places = tab + sd.tab_base;
+
+  /* in file order: the effective records' numbers, one behind the other */
+  if (!dense) {
+    u32 run_cnt = 0;
+    for (u32 c = 0; c < n_chunks; ++c) {
+      const u32 j = c * THREADS + tid;
+      const bool sel = j < n_walk && ((s_bits[j >> 5] >> (j & 31u)) & 1u);
+      s_cnt[tid] = sel ? 1u : 0u;
+      __syncthreads();
+      for (u32 off = 1; off < THREADS; off <<= 1) {
+        u32 tc = s_cnt[tid];
+        if (tid >= off) tc += s_cnt[tid - off];
+        __syncthreads();
+        s_cnt[tid] = tc;
+        __syncthreads();
+      }
+      if (sel) places[run_cnt + s_cnt[tid] - 1u] = j;
+      run_cnt += s_cnt[THREADS - 1];
+      __syncthreads();
+    }
+  }
+
+  /* the requests, in the caller's order */
+  u64 run_bytes = 0;
+  for (u32 base = 0; base < sd.req_n; base += THREADS) {
+    const u32 k = base + tid;
+    const bool valid = k < sd.req_n;
+    idx_rec r{};
+    u64 q = 0;
+    u32 kind = RGB_SEG_READ_OK;
+    if (valid) {
+      q = asked[k];
+      u32 lo = 0, hi = n_eff;                           /* lo = effective records whose Idx < q */
+      while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (ld_be64(index + (u64)rec_bytes * (dense ? mid : places[mid])) < q) lo = mid + 1u; else hi = mid;
+      }
+      if (lo < n_eff) r = decode_rec(index + (u64)rec_bytes * (dense ? lo : places[lo]), v2);
+      if (lo == n_eff || r.idx != q) kind = RGB_SEG_READ_MISSING;
+      else if (r.off > sd.n_bytes || r.len > sd.n_bytes - r.off) kind = RGB_SEG_READ_TRUNCATED;
+    }
+    const bool good = valid && kind == RGB_SEG_READ_OK;
+    const u32 len = good && !no_data ? r.len : 0u;      /* the bytes of `out` the row takes */
+    s_wide[tid] = len;
+    __syncthreads();
+    for (u32 off = 1; off < THREADS; off <<= 1) {
+      u64 tb = s_wide[tid];
+      if (tid >= off) tb += s_wide[tid - off];
+      __syncthreads();
+      s_wide[tid] = tb;
+      __syncthreads();
+    }
+    if (good) {
+      const u64 pre = run_bytes + s_wide[tid] - len;
+      rd_row w;
+      w.idx = r.idx; w.term = r.term; w.off = no_data ? sd.offset + r.off : pre; w.len = r.len; w.crc = r.crc;
+      rows[k] = w;
+      if (!no_data) {
+        rd_plan p;
+        p.src_off = sd.offset + r.off; p.pre = pre; p.src = s; p.pos = k; p.len = r.len; p.crc = r.crc;
+        plan[sd.req_first + k] = p;
+      }
+    } else if (valid) {
+      rows[k] = missing_row(q);
+      if (!no_data) plan[sd.req_first + k] = no_plan();
+      atomic_min(kind == RGB_SEG_READ_MISSING ? &s_miss_k : &s_trunc_k, k);
+    }
+    run_bytes += s_wide[THREADS - 1];
+    __syncthreads();
+  }
+  if (tid == 0u) {
+    rd_done d{};
+    d.bytes = run_bytes;
+    d.bad_k = s_miss_k < s_trunc_k ? s_miss_k : s_trunc_k;            /* the first bad row of either kind */
+    if (d.bad_k != NONE32) {
+      d.kind = s_miss_k < s_trunc_k ? RGB_SEG_READ_MISSING : RGB_SEG_READ_TRUNCATED;
+      d.bad_idx = asked[d.bad_k];
+    }
+    done[s] = d;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void rgb_read_place_kernel(
+    const rd_src *__restrict__ srcs, u32 n_sources, const rd_done *__restrict__ done, u64 out_bytes,
+    u64 *__restrict__ byte_base, u32 *__restrict__ crc_k, work_hdr *__restrict__ hdr, void *results_v, void *total_v) {
+  __shared__ u64 s_wide[THREADS];
+  __shared__ u32 s_bad;
+  const u32 tid = threadIdx.x;
+  rgb_seg_read_result *results = reinterpret_cast<rgb_seg_read_result *>(results_v);
+  if (tid == 0u) s_bad = 0u;
+  u64 run_bytes = 0;
+  u32 my_bad = 0;
+  for (u32 base = 0; base < n_sources; base += THREADS) {
+    const u32 s = base + tid;
+    const bool valid = s < n_sources;
+    rd_done d{};
+    if (valid) d = done[s];
+    s_wide[tid] = d.bytes;
+    __syncthreads();
+    for (u32 off = 1; off < THREADS; off <<= 1) {
+      u64 tb = s_wide[tid];
+      if (tid >= off) tb += s_wide[tid - off];
+      __syncthreads();
+      s_wide[tid] = tb;
+      __syncthreads();
+    }
+    if (valid) {
+      byte_base[s] = run_bytes + s_wide[tid] - d.bytes;
+      crc_k[s] = NONE32;
+      rgb_seg_read_result res{};
+      res.status = d.kind;
+      res.n_read = d.kind == RGB_SEG_READ_OK ? srcs[s].req_n : d.bad_k;
+      res.index = d.bad_idx; res.data_bytes = d.bytes;
+      results[s] = res;
+      if (d.kind != RGB_SEG_READ_OK) my_bad += 1u;
+    }
+    run_bytes += s_wide[THREADS - 1];
+    __syncthreads();
+  }
+  if (my_bad) atomicAdd(&s_bad, my_bad);
+  __syncthreads();
+  if (tid == 0u) {
+    rgb_seg_read_total t{};
+    t.status = out_bytes < run_bytes ? RGB_SEG_READ_SPACE : RGB_SEG_READ_OK;
+    t.n_bad = s_bad; t.out_bytes = run_bytes;
+    hdr->status = t.status;
+    hdr->crc_fail = NONE32;
+    *reinterpret_cast<rgb_seg_read_total *>(total_v) = t;
+  }
+}
+
+template <int GROUP, bool VERIFY>
+__global__ __launch_bounds__(THREADS) void rgb_read_copy_kernel(
+    const rd_plan *__restrict__ plan, u32 n, const unsigned char *__restrict__ files, const u64 *__restrict__ byte_base,
+    const work_hdr *__restrict__ hdr, u32 *__restrict__ crc_k, void *rows_v, unsigned char *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) u32 lds[VERIFY ? LDS_WORDS : 4u];
+  const bool room = hdr->status == RGB_SEG_READ_OK;     /* decided before this launch: the same for every lane */
+  if (VERIFY && room) load_tables<GROUP>(lds);
+  constexpr u32 PER_BLOCK = THREADS / GROUP;
+  const u32 lane = threadIdx.x & (GROUP - 1);
+  rd_row *rows = reinterpret_cast<rd_row *>(rows_v);
+  for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
+    const u32 e = base + threadIdx.x / GROUP;
+    bool live = e < n;
+    rd_plan p{};
+    if (live) { p = plan[e]; live = p.src != NONE32; }  /* a request of no slice, a MISSING or TRUNCATED row */
+    u64 dst_off = 0;
+    if (live) dst_off = byte_base[p.src] + p.pre;
+    if (live && lane == 0u) rows[e].off = dst_off;
+    live = live && room;                                /* SPACE: the rows are final, `out` is not touched */
+    const u32 len = p.len;
+    const unsigned char *pay = files + p.src_off;
+    unsigned char *dst = out + dst_off;
+    const bool wide = live && len >= 16u;
+    u32 crc = 0;
+    if (VERIFY) crc = entry_crc<GROUP, true>(lds, pay, dst, len, live, lane);
+    else if (wide) copy_plain<GROUP>(pay, dst, len, lane);
+    if (live && lane == 0u) {
+      if (VERIFY) crc = lane0_crc<true>(lds, crc, pay, dst, len);
+      else if (!wide) for (u32 k = 0; k < len; ++k) dst[k] = pay[k];
+      if (VERIFY) {
+        /* the stored Crc, the source and the position are fetched again here (loads the compiler does not merge with
+         * the ones above): kept in registers across the copy they take the wavefront-per-row form from 8 to 7
+         * wavefronts per SIMD */
+        const u32 stored = __builtin_nontemporal_load(&plan[e].crc);
+        if (stored != 0u && crc != stored)
+          atomic_min(&crc_k[__builtin_nontemporal_load(&plan[e].src)], __builtin_nontemporal_load(&plan[e].pos));
+      }
+    }
+  }
+}
+
+/* VERIFY: per source the first mismatch in request order, once every workgroup of the copy is done; MISSING and
+ * TRUNCATED keep their place */
+__global__ __launch_bounds__(THREADS) void rgb_read_finish_kernel(
+    const rd_src *__restrict__ srcs, u32 n_sources, const u64 *__restrict__ req, const u32 *__restrict__ crc_k,
+    const work_hdr *__restrict__ hdr, void *results_v, void *total_v) {
+  __shared__ u32 s_new;
+  if (hdr->status != RGB_SEG_READ_OK) return;           /* the same for every lane */
+  rgb_seg_read_result *results = reinterpret_cast<rgb_seg_read_result *>(results_v);
+  if (threadIdx.x == 0u) s_new = 0u;
+  __syncthreads();
+  u32 mine = 0;
+  for (u32 s = threadIdx.x; s < n_sources; s += THREADS) {
+    const u32 k = crc_k[s];
+    if (k == NONE32 || results[s].status != RGB_SEG_READ_OK) continue;
+    results[s].status = RGB_SEG_READ_CRC;
+    results[s].n_read = k;
+    results[s].index = req[srcs[s].req_first + k];
+    mine += 1u;
+  }
+  if (mine) atomicAdd(&s_new, mine);
+  __syncthreads();
+  if (threadIdx.x == 0u) reinterpret_cast<rgb_seg_read_total *>(total_v)->n_bad += s_new;
 }
 
 /* ---- mem-table flush (include/ra_gpu_wal.h, "mem-table flush") ---------------------------------------------
@@ -1088,8 +1379,8 @@ struct stage {
   dev_buf entries, data, offsets;                     /* host-buffer forms: what goes up ... */
   dev_buf crcs, out, pieces, result;                  /* ... and what comes down */
   dev_buf partials;                                   /* STREAM_MAX_BLOCKS values + the one result of the host-buffer form */
-  pinned_upload compact_desc, flush_writers;          /* device forms: the host arrays of a call ... */
-  dev_buf compact_work, flush_work;                   /* ... and its scratch plan */
+  pinned_upload compact_desc, flush_writers, read_desc;   /* device forms: the host arrays of a call ... */
+  dev_buf compact_work, flush_work, read_work;        /* ... and its scratch plan */
 };
 std::recursive_mutex g_mu;     /* the host-buffer forms call the device forms with it held */
 /* never destroyed: a context that is still open when the process ends must not free through a runtime that is gone */
@@ -1587,4 +1878,130 @@ extern "C" int rgb_segment_flush(rgb_ctx *ctx, const rgb_seg_writer *writers, ui
     const int rc_rows = seg::copy_down(pieces, s.pieces, (size_t)res.n_pieces * sizeof(rgb_seg_piece), st);
     return rc_rows ? rc_rows : seg::copy_down(out, s.out, (size_t)res.out_bytes, st);
   });
+}
+
+/* ---- reading entries back: read plans, folds and term queries over many segment files ------------------- */
+
+extern "C" int rgb_seg_read_check(const rgb_seg_read_source *sources, uint32_t n_sources, uint64_t files_bytes,
+                                  uint32_t n_req, uint32_t flags, uint32_t *covered, uint64_t *sum_bytes,
+                                  uint64_t *out_bound);
+
+extern "C" int rgb_segment_read_device(rgb_ctx *ctx, const rgb_seg_read_source *sources, uint32_t n_sources,
+                                       const void *d_files, uint64_t files_bytes, const uint64_t *req, uint32_t n_req,
+                                       uint32_t flags, void *d_rows, void *d_out, uint64_t out_bytes, void *d_results,
+                                       void *d_total, void *stream) {
+  if (!ctx || !d_total || (n_sources && (!sources || !d_results)) || (files_bytes && !d_files) || (n_req && !req) ||
+      (out_bytes && !d_out))
+    return RGB_E_INVAL;
+  uint32_t covered = 0;
+  uint64_t sum_bytes = 0;
+  int rc = rgb_seg_read_check(sources, n_sources, files_bytes, n_req, flags, &covered, &sum_bytes, nullptr);
+  if (rc) return rc;
+  if (covered && !d_rows) return RGB_E_INVAL;
+  const bool no_data = (flags & RGB_SEG_READ_NO_DATA) != 0u, verify = (flags & RGB_SEG_READ_VERIFY) != 0u;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  /* the sources and the requests, through the context's pinned buffer */
+  const size_t off_req = (size_t)n_sources * sizeof(seg::rd_src);
+  const size_t need = off_req + (size_t)n_req * 8u + 16u;
+  seg::pinned_upload &up = s.read_desc;
+  if ((rc = up.prepare(need))) return rc;
+  seg::rd_src *h_srcs = (seg::rd_src *)up.h;
+  uint64_t tab_total = 0;                               /* a source walks at most (n_bytes - 8) / 28 records */
+  for (uint32_t i = 0; i < n_sources; ++i) {
+    seg::rd_src d;
+    d.offset = sources[i].offset; d.n_bytes = sources[i].n_bytes;
+    d.req_first = sources[i].req_first; d.req_n = sources[i].req_n; d.tab_base = tab_total;
+    h_srcs[i] = d;
+    const uint64_t fit = d.n_bytes < RGB_SEG_HEADER_BYTES ? 0u : (d.n_bytes - RGB_SEG_HEADER_BYTES) / RGB_SEG_RECORD_BYTES_V1;
+    tab_total += fit < 65535u ? fit : 65535u;
+  }
+  if (n_req) memcpy((unsigned char *)up.h + off_req, req, (size_t)n_req * 8u);
+  /* the scratch: what resolve leaves per source, the sources' first bytes and first mismatches, the status, a plan
+   * record per request, the tables of effective records */
+  const size_t off_base = (size_t)n_sources * sizeof(seg::rd_done);
+  const size_t off_crc = off_base + (size_t)n_sources * 8u;
+  const size_t off_hdr = seg::up16(off_crc + (size_t)n_sources * 4u);
+  const size_t off_plan = off_hdr + sizeof(seg::work_hdr);
+  const size_t off_tab = off_plan + (no_data ? 0u : (size_t)n_req * sizeof(seg::rd_plan));
+  if (s.read_work.reserve(off_tab + (size_t)tab_total * 4u + 16u)) return RGB_E_NOMEM;
+  if ((rc = up.upload(need, st))) return rc;
+  unsigned char *w = (unsigned char *)s.read_work.p;
+  const seg::rd_src *d_srcs = (const seg::rd_src *)up.d.p;
+  const seg::u64 *d_req = (const seg::u64 *)((unsigned char *)up.d.p + off_req);
+  seg::rd_done *d_done = (seg::rd_done *)w;
+  seg::u64 *d_base = (seg::u64 *)(w + off_base);
+  seg::u32 *d_crc_k = (seg::u32 *)(w + off_crc);
+  seg::work_hdr *d_hdr = (seg::work_hdr *)(w + off_hdr);
+  seg::rd_plan *d_plan = (seg::rd_plan *)(w + off_plan);
+  seg::u32 *d_tab = (seg::u32 *)(w + off_tab);
+  /* requests that no slice names keep src = NONE32 in their plan record: the copy passes them by */
+  if (!no_data && covered != n_req &&
+      hipMemsetAsync(d_plan, 0xFF, (size_t)n_req * sizeof(seg::rd_plan), st) != hipSuccess)
+    return RGB_E_HIP;
+  (void)hipGetLastError();
+  if (n_sources)
+    hipLaunchKernelGGL(seg::rgb_read_resolve_kernel, dim3(n_sources), dim3(seg::THREADS), 0, st, d_srcs,
+                       (const unsigned char *)d_files, d_req, no_data ? 1u : 0u, d_tab, d_rows, d_plan, d_done);
+  hipLaunchKernelGGL(seg::rgb_read_place_kernel, dim3(1), dim3(seg::THREADS), 0, st, d_srcs, n_sources,
+                     (const seg::rd_done *)d_done, (seg::u64)out_bytes, d_base, d_crc_k, d_hdr, d_results, d_total);
+  if (no_data || !covered) return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+  const seg::u32 width = seg::group_width(sum_bytes / (n_req ? n_req : 1u));
+  seg::with_width(width, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    auto *copy = verify ? seg::rgb_read_copy_kernel<G, true> : seg::rgb_read_copy_kernel<G, false>;
+    hipLaunchKernelGGL(copy, dim3(seg::entry_grid(n_req, width)), dim3(seg::THREADS), 0, st, (const seg::rd_plan *)d_plan,
+                       n_req, (const unsigned char *)d_files, (const seg::u64 *)d_base, (const seg::work_hdr *)d_hdr,
+                       d_crc_k, d_rows, (unsigned char *)d_out);
+  });
+  if (verify)
+    hipLaunchKernelGGL(seg::rgb_read_finish_kernel, dim3(1), dim3(seg::THREADS), 0, st, d_srcs, n_sources, d_req,
+                       (const seg::u32 *)d_crc_k, (const seg::work_hdr *)d_hdr, d_results, d_total);
+  return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_segment_read(rgb_ctx *ctx, const rgb_seg_read_source *sources, uint32_t n_sources, const void *files,
+                                uint64_t files_bytes, const uint64_t *req, uint32_t n_req, uint32_t flags,
+                                rgb_seg_entry *rows, void *out, uint64_t out_bytes, rgb_seg_read_result *results,
+                                rgb_seg_read_total *total) {
+  if (!ctx || !total || (n_sources && (!sources || !results)) || (files_bytes && !files) || (n_req && !req) ||
+      (out_bytes && !out))
+    return RGB_E_INVAL;
+  uint32_t covered = 0;
+  uint64_t bound = 0;
+  int rc = rgb_seg_read_check(sources, n_sources, files_bytes, n_req, flags, &covered, nullptr, &bound);
+  if (rc) return rc;
+  if (covered && !rows) return RGB_E_INVAL;
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  const uint64_t room = out_bytes < bound ? out_bytes : bound;             /* the call never needs more than the bound */
+  const size_t res_bytes = (size_t)n_sources * sizeof(rgb_seg_read_result), off_total = seg::up16(res_bytes);
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (s.out.reserve((size_t)room + 16u) || s.entries.reserve((size_t)n_req * sizeof(rgb_seg_entry) + 16u) ||
+      s.result.reserve(off_total + sizeof(rgb_seg_read_total)))
+    return RGB_E_NOMEM;
+  if ((rc = seg::stage_in(s.data, files, (size_t)files_bytes, st))) return rc;
+  unsigned char *d_res = (unsigned char *)s.result.p;
+  rc = rgb_segment_read_device(ctx, sources, n_sources, s.data.p, files_bytes, req, n_req, flags, s.entries.p,
+                               room ? s.out.p : nullptr, room, d_res, d_res + off_total, st);
+  if (rc) return rc;
+  rgb_seg_read_total t;
+  if (hipMemcpyAsync(&t, d_res + off_total, sizeof t, hipMemcpyDeviceToHost, st) != hipSuccess) return RGB_E_HIP;
+  if ((rc = seg::fetch(results, s.result, res_bytes, st))) return rc;
+  /* only the rows that slices name come back (neighbouring slices in one copy), and only the bytes of a good answer */
+  for (uint32_t i = 0; i < n_sources;) {
+    const uint32_t first = sources[i].req_first;
+    uint32_t end = first + sources[i].req_n;
+    for (++i; i < n_sources && sources[i].req_first == end; ++i) end += sources[i].req_n;
+    if (end > first && hipMemcpyAsync(rows + first, (const rgb_seg_entry *)s.entries.p + first,
+                                      (size_t)(end - first) * sizeof(rgb_seg_entry), hipMemcpyDeviceToHost,
+                                      st) != hipSuccess)
+      return RGB_E_HIP;
+  }
+  if (t.status == RGB_SEG_READ_OK && (rc = seg::copy_down(out, s.out, (size_t)t.out_bytes, st))) return rc;
+  if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  *total = t;
+  return RGB_OK;
 }

@@ -1,10 +1,11 @@
 /*
  * rgb_segment_host.cpp -- the host-only half of the segment part of include/ra_gpu_wal.h: the file layout and the
  * index walk of a segment file (src/ra_log_segment.erl:1118-1138, 1197-1219), and the descriptor checks of a compaction
- * group and of a mem-table flush.  No HIP here, so the file also builds on its own under the sanitizers
- * (tests/test_segment.py::test_segment_scan_under_sanitizers,
+ * group, of a mem-table flush and of a batched read.  No HIP here, so the file also builds on its own under the
+ * sanitizers (tests/test_segment.py::test_segment_scan_under_sanitizers,
  * tests/test_segment_compact.py::test_compact_descriptors_under_sanitizers,
- * tests/test_segment_flush.py::test_flush_descriptors_under_sanitizers).
+ * tests/test_segment_flush.py::test_flush_descriptors_under_sanitizers,
+ * tests/test_segment_read.py::test_read_descriptors_under_sanitizers).
  */
 #include <stdint.h>
 #include "../../include/ra_gpu_wal.h"
@@ -116,6 +117,34 @@ extern "C" int rgb_segment_flush_bound(const rgb_seg_writer *writers, uint32_t n
   if (data_bytes + per_entry < data_bytes) return RGB_E_INVAL;
   *out_bound = data_bytes + per_entry;
   *pieces_bound = n_entries;
+  return RGB_OK;
+}
+
+/* ---- reading entries back: the sources of a call, checked before anything is enqueued ---------------------
+ * Library-internal (rgb_segment.hip calls it; not in the header), shared by both forms.  *covered = the requests the
+ * slices name, *sum_bytes = the sum of the sources' n_bytes (saturating), *out_bound = a size of `out` that always
+ * suffices: the sum of req_n * n_bytes (saturating). */
+extern "C" int rgb_seg_read_check(const rgb_seg_read_source *sources, uint32_t n_sources, uint64_t files_bytes,
+                                  uint32_t n_req, uint32_t flags, uint32_t *covered, uint64_t *sum_bytes,
+                                  uint64_t *out_bound) {
+  if (n_sources > RGB_SEG_READ_MAX_SOURCES || (n_sources && !sources)) return RGB_E_INVAL;
+  if (flags & ~(RGB_SEG_READ_VERIFY | RGB_SEG_READ_NO_DATA)) return RGB_E_INVAL;
+  if ((flags & RGB_SEG_READ_VERIFY) && (flags & RGB_SEG_READ_NO_DATA)) return RGB_E_INVAL;
+  uint64_t next = 0, named = 0, sum = 0, bound = 0;              /* next: the first request a later slice may name */
+  for (uint32_t s = 0; s < n_sources; ++s) {
+    const rgb_seg_read_source &src = sources[s];
+    if (src.offset > files_bytes || src.n_bytes > files_bytes - src.offset) return RGB_E_INVAL;
+    if (src.req_first > n_req || src.req_n > n_req - src.req_first) return RGB_E_INVAL;
+    if (src.req_first < next) return RGB_E_INVAL;                  /* ascending and disjoint */
+    next = (uint64_t)src.req_first + src.req_n;
+    named += src.req_n;
+    sum = sum + src.n_bytes < sum ? ~0ull : sum + src.n_bytes;
+    const uint64_t most = src.req_n && src.n_bytes > ~0ull / src.req_n ? ~0ull : src.n_bytes * src.req_n;
+    bound = bound + most < bound ? ~0ull : bound + most;
+  }
+  if (covered) *covered = (uint32_t)named;                         /* <= n_req: the slices are disjoint */
+  if (sum_bytes) *sum_bytes = sum;
+  if (out_bound) *out_bound = bound;
   return RGB_OK;
 }
 

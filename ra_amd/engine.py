@@ -48,7 +48,8 @@ WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "r
                "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
                "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate",
                "rgb_segment_compact_bound", "rgb_segment_info_device", "rgb_segment_info", "rgb_segment_compact_device",
-               "rgb_segment_compact", "rgb_segment_flush_bound", "rgb_segment_flush_device", "rgb_segment_flush"]                                                                                 # include/ra_gpu_wal.h
+               "rgb_segment_compact", "rgb_segment_flush_bound", "rgb_segment_flush_device", "rgb_segment_flush",
+               "rgb_segment_read_device", "rgb_segment_read"]                                                                                 # include/ra_gpu_wal.h
 
 
 class RgbError(RuntimeError):
@@ -218,6 +219,8 @@ def lib():
     L.rgb_segment_flush_device.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp,
                                            C.c_uint64, vp, vp]
     L.rgb_segment_flush.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp, C.c_uint64, vp]
+    L.rgb_segment_read_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, u32, vp, vp, C.c_uint64, vp, vp, vp]
+    L.rgb_segment_read.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, u32, vp, vp, C.c_uint64, vp, vp]
     if L.rgb_abi_version() != abi.ABI_VERSION and not (os.environ.get("RGB_LIB") and L.rgb_abi_version() == abi.ABI_VERSION - 1):
         raise RuntimeError("ABI version mismatch")     # (RGB_LIB=<the previous ABI's build>: A/B timing, tools/ only)
     for i, dt in enumerate(abi.STRUCT_DTYPES):
@@ -742,6 +745,51 @@ class RaGpuBatch:
         if int(res["status"][0]) != abi.SEG_FLUSH_OK:
             return res[0], None, None
         return res[0], pieces[:int(res["n_pieces"][0])], out[:int(res["out_bytes"][0])]
+
+    # -- reading entries back: read plans, folds and term queries over many segment files (include/ra_gpu_wal.h) --
+    def segment_read_device(self, sources: np.ndarray, d_files: int, files_bytes: int, req, d_rows: int, d_out: int,
+                            out_bytes: int, d_results: int, d_total: int, flags: int = 0, stream: int = 0):
+        """One abi.SEG_ENTRY_DTYPE row per requested index into d_rows, the payloads back to back in request order into
+        d_out, one abi.SEG_READ_RESULT_DTYPE row per source into d_results, one abi.SEG_READ_TOTAL_DTYPE record into
+        d_total (ra_log_segment:read_sparse/4, fold/6 and term_query/2 over many files).  `sources`
+        (abi.SEG_READ_SOURCE_DTYPE) and `req` (uint64 indexes) are host arrays; enqueues and returns."""
+        sources = np.ascontiguousarray(sources, dtype=abi.SEG_READ_SOURCE_DTYPE)
+        req = np.ascontiguousarray(req, dtype=np.uint64)
+        self._check(self._L.rgb_segment_read_device(self._h, sources.ctypes.data if len(sources) else None, len(sources),
+                                                    d_files or None, files_bytes, req.ctypes.data if len(req) else None,
+                                                    len(req), flags, d_rows or None, d_out or None, out_bytes,
+                                                    d_results or None, d_total or None, stream or None),
+                    "rgb_segment_read_device")
+
+    def segment_read(self, sources: np.ndarray, files: np.ndarray, req, flags: int = 0, rows: np.ndarray | None = None,
+                     out: np.ndarray | None = None):
+        """Host-buffer form: (total record, result rows, rows, out bytes).  `rows` (abi.SEG_ENTRY_DTYPE, one per
+        request; only those a slice names are written) defaults to a zeroed array.  Without `out` the call sizes it
+        itself (a sizing call first, unless abi.SEG_READ_NO_DATA is set); with `out` the bytes are `out[:out_bytes]`
+        when the total's status is abi.SEG_READ_OK and None when it is abi.SEG_READ_SPACE."""
+        sources = np.ascontiguousarray(sources, dtype=abi.SEG_READ_SOURCE_DTYPE)
+        files = np.ascontiguousarray(files, dtype=np.uint8)
+        req = np.ascontiguousarray(req, dtype=np.uint64)
+        if rows is None:
+            rows = np.zeros(len(req), dtype=abi.SEG_ENTRY_DTYPE)
+        results = np.zeros(len(sources), dtype=abi.SEG_READ_RESULT_DTYPE)
+        total = np.zeros(1, dtype=abi.SEG_READ_TOTAL_DTYPE)
+
+        def call(buf):
+            self._check(self._L.rgb_segment_read(self._h, sources.ctypes.data if len(sources) else None, len(sources),
+                                                 files.ctypes.data if len(files) else None, len(files),
+                                                 req.ctypes.data if len(req) else None, len(req), flags,
+                                                 rows.ctypes.data if len(rows) else None,
+                                                 buf.ctypes.data if buf is not None and len(buf) else None,
+                                                 0 if buf is None else len(buf), results.ctypes.data if len(sources) else None,
+                                                 total.ctypes.data), "rgb_segment_read")
+        call(out)
+        if out is None and int(total["status"][0]) == abi.SEG_READ_SPACE:
+            out = np.zeros(int(total["out_bytes"][0]), dtype=np.uint8)
+            call(out)
+        if int(total["status"][0]) != abi.SEG_READ_OK:
+            return total[0], results, rows, None
+        return total[0], results, rows, (out[:int(total["out_bytes"][0])] if out is not None else np.zeros(0, dtype=np.uint8))
 
     # -- observability -----------------------------------------------------------------
     def snapshot(self) -> np.ndarray:
