@@ -22,6 +22,7 @@
 -export([segment_info/4, segment_compact/6, segment_compact_group/4]).
 -export([segment_flush/7, segment_flush_batch/5]).
 -export([segment_read/5, segment_read_plan/3, segment_term_query_batch/2]).
+-export([crc32_spans/3, snapshot_build/3, snapshot_validate/3, snapshot_images/2, snapshot_recover_batch/2, accept_chunks/2]).
 -export([encode_msg/3, encode_msgs/1, decode_decision/1, decision_to_effects/3]).
 
 -include_lib("ra/src/ra.hrl").
@@ -315,6 +316,86 @@ read_plan_answers([{_FileBin, Idxs} | Plan], <<St:32/little, NRead:32/little, Id
     N = length(Idxs),
     [Answer(St, NRead, Idx, binary:part(RowsBin, 32 * First, 32 * N)) |
      read_plan_answers(Plan, Results, RowsBin, First + N, Answer)].
+
+%% snapshots and checkpoints (src/ra_log_snapshot.erl, src/ra_snapshot.erl:343-479, 1008-1059): ragged CRC batches, the
+%% snapshot.dat / indexes images and their validation, for many members in one call.  All records little endian.
+%% SpansBin = one 32-byte record per span: offset:64, n_bytes:64 (inside DataBin), init:32, 0:96; CrcsBin = Crc:32 each.
+%% ItemsBin = one 40-byte record per image: kind:32 (0 snapshot, 1 indexes), meta_len:32, meta_offset:64,
+%% data_offset:64, data_bytes:64 (inside DataBin), out_offset:64 (filled by the NIF); ImagesBin = the images back to back.
+%% FilesBin = one 32-byte record per file: offset:64, n_bytes:64 (inside BytesBin), kind:32, flags:32 (1 = the header
+%% alone, read_meta/1), 0:64; InfosBin = one 48-byte record per file: status:32 (0 ok, 1 invalid_format,
+%% 2 invalid_version, 3 checksum_error, 4 bad meta, 5 eof), version:32, stored_crc:32, computed_crc:32, meta_offset:64,
+%% meta_len:32, 0:32, data_offset:64, data_bytes:64 (offsets into BytesBin).
+crc32_spans(_Ctx, _SpansBin, _DataBin) -> erlang:nif_error(not_loaded).
+snapshot_build(_Ctx, _ItemsBin, _DataBin) -> erlang:nif_error(not_loaded).
+snapshot_validate(_Ctx, _FilesBin, _BytesBin) -> erlang:nif_error(not_loaded).
+
+%% Snapshots = [{MetaBin, DataIoList}] (MetaBin = term_to_binary(Meta), DataIoList = term_to_iovec(MacState)) ->
+%% {ok, [ImageBin]}: what ra_log_snapshot:write/4 hands to ra_lib:write_file/3 (:49-68), for every member that writes a
+%% snapshot or checkpoint after a WAL roll-over.  term_to_binary / term_to_iovec, file I/O and fsync stay with the caller.
+snapshot_images(Ctx, Snapshots) ->
+    {ItemsBin, Data, _, Sizes} =
+        lists:foldl(fun({MetaBin, DataIoList}, {I, D, Off, S}) ->
+                            MLen = byte_size(MetaBin),
+                            DLen = iolist_size(DataIoList),
+                            {<<I/binary, 0:32/little, MLen:32/little, Off:64/little, (Off + MLen):64/little,
+                               DLen:64/little, 0:64>>,
+                             [D, MetaBin, DataIoList], Off + MLen + DLen, [13 + MLen + DLen | S]}
+                    end, {<<>>, [], 0, []}, Snapshots),
+    case snapshot_build(Ctx, ItemsBin, iolist_to_binary(Data)) of
+        {ok, ImagesBin} -> {ok, split_images(ImagesBin, lists:reverse(Sizes))};
+        Error -> Error
+    end.
+
+split_images(<<>>, []) -> [];
+split_images(Bin, [Size | Sizes]) ->
+    <<Image:Size/binary, Rest/binary>> = Bin,
+    [Image | split_images(Rest, Sizes)].
+
+%% Files = [{FileBin, validate | read_meta}], the snapshot.dat bytes of a recovery batch -- per member its snapshot
+%% (validate), its newest checkpoint (validate), older checkpoints (read_meta): pick_first_valid/4, find_checkpoints/4,
+%% find_recovery_checkpoint/1 (src/ra_snapshot.erl:343-479).  -> {ok, [Answer]}, one per file, in order:
+%% {ok, MetaBin, DataBin} (for binary_to_term) | {error, invalid_format} | {error, {invalid_version, V}} |
+%% {error, checksum_error} | {error, bad_meta} (parse_snapshot/1 has no clause; read_meta: the short read) |
+%% {error, unexpected_eof_when_parsing_header}.  One file's error leaves the other files' answers as they are.
+%% Directory listing and sorting, which file to try next and what to delete stay in ra_snapshot.
+snapshot_recover_batch(Ctx, Files) ->
+    {FilesBin, Bytes, _} =
+        lists:foldl(fun({FileBin, Mode}, {F, B, Off}) ->
+                            Len = byte_size(FileBin),
+                            Flags = case Mode of validate -> 0; read_meta -> 1 end,
+                            {<<F/binary, Off:64/little, Len:64/little, 0:32/little, Flags:32/little, 0:64>>,
+                             [B, FileBin], Off + Len}
+                    end, {<<>>, [], 0}, Files),
+    BytesBin = iolist_to_binary(Bytes),
+    case snapshot_validate(Ctx, FilesBin, BytesBin) of
+        {ok, InfosBin} ->
+            {ok, [case St of
+                      0 -> {ok, binary:part(BytesBin, MOff, MLen), binary:part(BytesBin, DOff, DLen)};
+                      1 -> {error, invalid_format};
+                      2 -> {error, {invalid_version, V}};
+                      3 -> {error, checksum_error};
+                      4 -> {error, bad_meta};
+                      5 -> {error, unexpected_eof_when_parsing_header}
+                  end ||
+                     <<St:32/little, V:32/little, _Stored:32, _Computed:32, MOff:64/little, MLen:32/little, _:32,
+                       DOff:64/little, DLen:64/little>> <= InfosBin]};
+        Error ->
+            Error
+    end.
+
+%% Chunks = [{PartialCrc0, ChunkBin}], one per snapshot transfer in flight -> [PartialCrc]:
+%% erlang:crc32(PartialCrc0, Chunk) of accept_chunk/2 (src/ra_log_snapshot.erl:104-108); PartialCrc0 = 0 starts a
+%% checksum (begin_accept/2, :80-81).  The file:write of the chunk and the pwrite of the Crc at byte 5 in
+%% complete_accept/2 stay with the caller.
+accept_chunks(Ctx, Chunks) ->
+    {SpansBin, Data, _} =
+        lists:foldl(fun({Crc0, ChunkBin}, {S, D, Off}) ->
+                            Len = byte_size(ChunkBin),
+                            {<<S/binary, Off:64/little, Len:64/little, Crc0:32/little, 0:96>>, [D, ChunkBin], Off + Len}
+                    end, {<<>>, [], 0}, Chunks),
+    {ok, CrcsBin} = crc32_spans(Ctx, SpansBin, iolist_to_binary(Data)),
+    [Crc || <<Crc:32/little>> <= CrcsBin].
 
 %% The bytes of a whole segment file for Entries = [{Idx, Term, Bin}] in the caller's order: what
 %% ra_log_segment:append/4 accumulates in pending_index / pending_data and flush/1 writes

@@ -526,6 +526,110 @@ int rgb_segment_read(rgb_ctx *ctx, const rgb_seg_read_source *sources, uint32_t 
                      uint64_t files_bytes, const uint64_t *req, uint32_t n_req, uint32_t flags, rgb_seg_entry *rows,
                      void *out, uint64_t out_bytes, rgb_seg_read_result *results, rgb_seg_read_total *total);
 
+/* ==== snapshots and checkpoints: ragged CRC batches, file images and their validation ====================
+ *
+ * The snapshot family -- snapshot.dat of snapshots, checkpoints and recovery checkpoints (src/ra_log_snapshot.erl) and
+ * the `indexes` file beside it (src/ra_snapshot.erl:1008-1059) -- for many members in one call:
+ *   - recovery: pick_first_valid/4, find_checkpoints/4, find_recovery_checkpoint/1 (src/ra_snapshot.erl:343-479) call
+ *     Mod:validate/1 and Mod:read_meta/1 on every member's files            -> rgb_snapshot_validate
+ *   - writing: ra_log_snapshot:write/4 (:49-68), write_indexes/2             -> rgb_snapshot_build
+ *   - receiving: begin_accept/2 (:80-81), accept_chunk/2's erlang:crc32(PartialCrc0, Chunk) (:104-108) for every
+ *     transfer in flight                                                     -> rgb_crc32_spans
+ * A batch is RAGGED: items of a few hundred bytes beside items of gigabytes.  The work is split by bytes, not by item:
+ * short items get a group of lanes each, long ones are cut into 64 KiB blocks that all share one capped grid, and a
+ * per-item step joins the blocks.  The number of launches does not depend on the number of items (at most five).
+ *
+ * Descriptor arrays are HOST arrays in every form: validated on the host (RGB_E_INVAL, nothing enqueued: a span, piece,
+ * file or image outside its buffer, an unknown kind, unknown flags, meta_len != 0 on an indexes item, more than
+ * 2^31 - 1 items) and staged by the library.  n == 0 is legal.  Device forms enqueue on `stream` (NULL = the context's
+ * stream) and do not synchronise; host-buffer forms stage and synchronise.  The scratch lives in the context (released
+ * by rgb_close): one snapshot call per context at a time.  Only a span's own bytes are read and only an image's own
+ * bytes are written, whatever the alignment of the buffers.
+ *
+ * File I/O and fsync, the pwrite of the Crc at byte 5 in complete_accept/2, term_to_binary / term_to_iovec /
+ * binary_to_term, directory listing and sorting, and the decision which file to try next and what to delete stay with
+ * the caller. */
+typedef struct rgb_crc_span {          /* 32 bytes */
+  uint64_t offset, n_bytes;            /* the bytes = data[offset .. offset + n_bytes); any length, above 2^32 included */
+  uint32_t init, _pad;                 /* PartialCrc0; 0 starts a checksum */
+  uint64_t _pad2;
+} rgb_crc_span;
+
+/* d_crcs[i] = erlang:crc32(init_i, data[offset_i .. + n_bytes_i)) for the n spans.  Spans may overlap or name the same
+ * bytes. */
+int rgb_crc32_spans_device(rgb_ctx *ctx, const rgb_crc_span *spans, uint32_t n, const void *d_data, uint64_t data_bytes,
+                           void *d_crcs, void *stream);
+int rgb_crc32_spans(rgb_ctx *ctx, const rgb_crc_span *spans, uint32_t n, const void *data, uint64_t data_bytes,
+                    uint32_t *crcs);
+
+#define RGB_SNAP_KIND_SNAPSHOT 0u      /* <<"RASN", 1:8, Crc:32, MetaSize:32, Meta/binary, Data/binary>>,
+                                          Crc = crc32(<<MetaSize:32>>, Meta, Data) (src/ra_log_snapshot.erl:54-63) */
+#define RGB_SNAP_KIND_INDEXES  1u      /* <<"RASI", 1:8, Crc:32, Data/binary>>, Crc = crc32(Data)
+                                          (src/ra_snapshot.erl:1017-1026) */
+#define RGB_SNAP_HEADER_BYTES      9u  /* magic, Version, Crc */
+#define RGB_SNAP_META_HEADER_BYTES 13u /* ... and MetaSize */
+
+typedef struct rgb_snap_item {         /* 40 bytes: one image to write */
+  uint32_t kind;                       /* RGB_SNAP_KIND_* */
+  uint32_t meta_len;                   /* MetaSize; 0 for the indexes kind */
+  uint64_t meta_offset;                /* Meta = data[meta_offset .. + meta_len) */
+  uint64_t data_offset, data_bytes;    /* Data = data[data_offset .. + data_bytes) */
+  uint64_t out_offset;                 /* where the image starts in the output (rgb_snapshot_layout fills it) */
+} rgb_snap_item;
+
+/* Host helper, pure: out_offset of every item when the images (13 + meta_len + data_bytes bytes, the indexes kind
+ * 9 + data_bytes) are written back to back from `base`; returns the offset behind the last one. */
+uint64_t rgb_snapshot_layout(rgb_snap_item *items, uint32_t n, uint64_t base);
+
+/* d_out[out_offset ..) = the image of every item; every payload byte is read once, CRC and copy share the load.
+ * d_crcs (may be NULL) receives the Crc written into each image.  Images may not overlap. */
+int rgb_snapshot_build_device(rgb_ctx *ctx, const rgb_snap_item *items, uint32_t n, const void *d_data,
+                              uint64_t data_bytes, void *d_out, uint64_t out_bytes, void *d_crcs, void *stream);
+/* Host-buffer form: only the images' own bytes of `out` are written; crcs may be NULL. */
+int rgb_snapshot_build(rgb_ctx *ctx, const rgb_snap_item *items, uint32_t n, const void *data, uint64_t data_bytes,
+                       void *out, uint64_t out_bytes, uint32_t *crcs);
+
+typedef struct rgb_snap_file {         /* 32 bytes: one file to check */
+  uint64_t offset, n_bytes;            /* the file = files[offset .. offset + n_bytes) */
+  uint32_t kind;                       /* RGB_SNAP_KIND_* */
+  uint32_t flags;                      /* RGB_SNAP_META_ONLY */
+  uint64_t _pad;
+} rgb_snap_file;
+
+#define RGB_SNAP_META_ONLY 1u          /* read_meta_internal/1 (src/ra_log_snapshot.erl:234-253): the header alone, no CRC */
+
+/* recover/1 and validate/2 (src/ra_log_snapshot.erl:176-187, 255-261), indexes/1 (src/ra_snapshot.erl:1028-1059), in
+ * this order: */
+#define RGB_SNAP_OK              0u
+#define RGB_SNAP_INVALID_FORMAT  1u    /* fewer than 9 bytes, or other magic.  The indexes kind: the legacy file without
+                                          a header (:1046-1054) -- the caller tries binary_to_term */
+#define RGB_SNAP_INVALID_VERSION 2u    /* magic good, at least 9 bytes, Version /= 1: `version` holds it.  META_ONLY, the
+                                          snapshot kind: also 9 .. 12 bytes with good magic, even with Version 1 -- the
+                                          reference's second clause of read_meta_internal/1 */
+#define RGB_SNAP_CHECKSUM        3u    /* crc32 of everything behind byte 9 /= the stored Crc.  A stored 0 is NOT
+                                          "unchecked" here, unlike segments: it must equal the computed value */
+#define RGB_SNAP_BAD_META        4u    /* the snapshot kind: parse_snapshot/1 (:263-266) has no clause -- fewer than 4
+                                          bytes behind byte 9, or MetaSize > n_bytes - 13 (META_ONLY: the short read) */
+#define RGB_SNAP_EOF             5u    /* META_ONLY: 0 bytes (unexpected_eof_when_parsing_header) */
+
+typedef struct rgb_snap_info {         /* 48 bytes, one per file */
+  uint32_t status;                     /* RGB_SNAP_* */
+  uint32_t version;                    /* INVALID_VERSION and behind; 0 before */
+  uint32_t stored_crc;                 /* the header's Crc: INVALID_VERSION and behind */
+  uint32_t computed_crc;               /* CHECKSUM, BAD_META, OK; 0 with META_ONLY */
+  uint64_t meta_offset;                /* OK only, offsets into the files buffer: Meta ...                          */
+  uint32_t meta_len, _pad;
+  uint64_t data_offset, data_bytes;    /* ... and what follows it: what parse_snapshot/1 hands to binary_to_term    */
+} rgb_snap_info;
+
+/* d_infos[i] = the row of file i (8-byte aligned, device memory).  Files fail independently: one bad file leaves every
+ * other row as it would have been.  The CRC of a file is computed whenever it has 9 bytes or more and META_ONLY is not
+ * set.  META_ONLY on the indexes kind checks magic and Version alone. */
+int rgb_snapshot_validate_device(rgb_ctx *ctx, const rgb_snap_file *files, uint32_t n, const void *d_files,
+                                 uint64_t files_bytes, void *d_infos, void *stream);
+int rgb_snapshot_validate(rgb_ctx *ctx, const rgb_snap_file *files, uint32_t n, const void *bytes, uint64_t files_bytes,
+                          rgb_snap_info *infos);
+
 #ifdef __cplusplus
 }
 #endif

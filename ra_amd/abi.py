@@ -195,6 +195,20 @@ assert (SEG_READ_SOURCE_DTYPE.itemsize, SEG_READ_RESULT_DTYPE.itemsize, SEG_READ
 (SEG_READ_OK, SEG_READ_MISSING, SEG_READ_TRUNCATED, SEG_READ_CRC, SEG_READ_BAD_SOURCE, SEG_READ_SPACE) = range(6)
 SEG_READ_VERIFY, SEG_READ_NO_DATA = 1, 2
 SEG_READ_MAX_SOURCES = 65536
+# snapshots and checkpoints (same header): a span of a ragged CRC batch, an image to write, a file to check, its row
+CRC_SPAN_DTYPE = np.dtype([("offset", u64), ("n_bytes", u64), ("init", u32), ("_pad", u32), ("_pad2", u64)])
+SNAP_ITEM_DTYPE = np.dtype([("kind", u32), ("meta_len", u32), ("meta_offset", u64), ("data_offset", u64),
+                            ("data_bytes", u64), ("out_offset", u64)])
+SNAP_FILE_DTYPE = np.dtype([("offset", u64), ("n_bytes", u64), ("kind", u32), ("flags", u32), ("_pad", u64)])
+SNAP_INFO_DTYPE = np.dtype([("status", u32), ("version", u32), ("stored_crc", u32), ("computed_crc", u32),
+                            ("meta_offset", u64), ("meta_len", u32), ("_pad", u32), ("data_offset", u64),
+                            ("data_bytes", u64)])
+assert (CRC_SPAN_DTYPE.itemsize, SNAP_ITEM_DTYPE.itemsize, SNAP_FILE_DTYPE.itemsize, SNAP_INFO_DTYPE.itemsize) == \
+    (32, 40, 32, 48)
+SNAP_KIND_SNAPSHOT, SNAP_KIND_INDEXES = 0, 1
+SNAP_HEADER_BYTES, SNAP_META_HEADER_BYTES = 9, 13
+SNAP_META_ONLY = 1
+(SNAP_OK, SNAP_INVALID_FORMAT, SNAP_INVALID_VERSION, SNAP_CHECKSUM, SNAP_BAD_META, SNAP_EOF) = range(6)
 
 # rgb_view (ABI v9, rgb_collect_view): pointers into the pinned slot the device wrote
 VIEW_DTYPE = np.dtype([("decisions", "<u8"), ("rpcs", "<u8"), ("tick", "<u8"), ("n", "<u4"), ("n_rpcs", "<u4"),

@@ -872,6 +872,72 @@ static ERL_NIF_TERM nif_segment_read(ErlNifEnv *env, int argc, const ERL_NIF_TER
                           enif_make_binary(env, &out));
 }
 
+/* crc32_spans(Ctx, SpansBin, DataBin) -> {ok, CrcsBin}: SpansBin = n rgb_crc_span records (offset, n_bytes, init),
+ * DataBin = the bytes they point into; CrcsBin = n native 32-bit values, erlang:crc32(Init, Span) each -- accept_chunk/2
+ * of every snapshot transfer in flight, begin_accept/2, write_indexes/2 (src/ra_log_snapshot.erl:80-81, 104-108;
+ * src/ra_snapshot.erl:1020, 1038) */
+static ERL_NIF_TERM nif_crc32_spans(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary s, d, out;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &s) || !enif_inspect_binary(env, argv[2], &d) ||
+      s.size % sizeof(rgb_crc_span) != 0 || s.size / sizeof(rgb_crc_span) > 0x7FFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(s.size / sizeof(rgb_crc_span));
+  if (!enif_alloc_binary((size_t)(n ? n : 1) * sizeof(uint32_t), &out)) return mk_error(env, c, RGB_E_NOMEM);
+  int rc = rgb_crc32_spans(c->ctx, (const rgb_crc_span *)s.data, n, d.data, d.size, (uint32_t *)out.data);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  enif_realloc_binary(&out, (size_t)n * sizeof(uint32_t));
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+}
+
+/* snapshot_build(Ctx, ItemsBin, DataBin) -> {ok, ImagesBin}: ItemsBin = n rgb_snap_item records (out_offset is filled
+ * here, back to back from 0), DataBin = the Meta and Data bytes they point into; ImagesBin = the snapshot.dat / indexes
+ * images back to back, what ra_log_snapshot:write/4 and write_indexes/2 hand to ra_lib:write_file/3
+ * (src/ra_log_snapshot.erl:49-68, src/ra_snapshot.erl:1017-1026) */
+static ERL_NIF_TERM nif_snapshot_build(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary it, d, out;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &it) || !enif_inspect_binary(env, argv[2], &d) ||
+      it.size % sizeof(rgb_snap_item) != 0 || it.size / sizeof(rgb_snap_item) > 0x7FFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(it.size / sizeof(rgb_snap_item));
+  rgb_snap_item *items = (rgb_snap_item *)enif_alloc(it.size ? it.size : 1);
+  if (!items) return mk_error(env, c, RGB_E_NOMEM);
+  memcpy(items, it.data, it.size);                      /* binaries are immutable: lay out a copy */
+  const uint64_t total = rgb_snapshot_layout(items, n, 0);
+  /* a descriptor outside DataBin is refused before its sizes are believed */
+  for (uint32_t i = 0; i < n; ++i)
+    if (items[i].data_offset > d.size || items[i].data_bytes > d.size - items[i].data_offset ||
+        items[i].meta_offset > d.size || items[i].meta_len > d.size - items[i].meta_offset) {
+      enif_free(items);
+      return mk_error(env, c, RGB_E_INVAL);
+    }
+  if (!enif_alloc_binary((size_t)(total ? total : 1), &out)) { enif_free(items); return mk_error(env, c, RGB_E_NOMEM); }
+  int rc = rgb_snapshot_build(c->ctx, items, n, d.data, d.size, out.data, total, NULL);
+  enif_free(items);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  enif_realloc_binary(&out, (size_t)total);
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+}
+
+/* snapshot_validate(Ctx, FilesBin, BytesBin) -> {ok, InfosBin}: FilesBin = n rgb_snap_file records (offset, n_bytes,
+ * kind, flags), BytesBin = the files' bytes; InfosBin = one rgb_snap_info record per file -- recover/1, validate/1 and,
+ * with flag 1, read_meta/1 of every member's snapshot and checkpoints on start (src/ra_log_snapshot.erl:176-266,
+ * src/ra_snapshot.erl:343-479, 1028-1059) */
+static ERL_NIF_TERM nif_snapshot_validate(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary f, b, out;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &f) || !enif_inspect_binary(env, argv[2], &b) ||
+      f.size % sizeof(rgb_snap_file) != 0 || f.size / sizeof(rgb_snap_file) > 0x7FFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(f.size / sizeof(rgb_snap_file));
+  if (!enif_alloc_binary((size_t)(n ? n : 1) * sizeof(rgb_snap_info), &out)) return mk_error(env, c, RGB_E_NOMEM);
+  int rc = rgb_snapshot_validate(c->ctx, (const rgb_snap_file *)f.data, n, b.data, b.size, (rgb_snap_info *)out.data);
+  if (rc) { enif_release_binary(&out); return mk_error(env, c, rc); }
+  enif_realloc_binary(&out, (size_t)n * sizeof(rgb_snap_info));
+  return enif_make_tuple2(env, enif_make_atom(env, "ok"), enif_make_binary(env, &out));
+}
+
 static ErlNifFunc nif_funcs[] = {
   {"open", 4, nif_open, 0},
   {"register_groups", 3, nif_register_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
@@ -902,6 +968,9 @@ static ErlNifFunc nif_funcs[] = {
   {"segment_compact", 6, nif_segment_compact, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_flush", 7, nif_segment_flush, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_read", 5, nif_segment_read, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"crc32_spans", 3, nif_crc32_spans, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"snapshot_build", 3, nif_snapshot_build, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"snapshot_validate", 3, nif_snapshot_validate, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(ra_gpu_batch, nif_funcs, on_load, NULL, NULL, NULL)

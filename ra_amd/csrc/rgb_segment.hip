@@ -5,7 +5,9 @@
  *   - the whole segment file image in one pass      (src/ra_log_segment.erl:1118-1122, 1211-1219)
  *   - one long buffer with a starting value         (src/ra_log_snapshot.erl:57-107, 256; src/ra_snapshot.erl:1020, 1038)
  * and, behind them, major compaction: info/2 of the files of a group and the copy of their live entries into one new
- * segment (src/ra_log_segment.erl:736-790, 819-908; src/ra_log_segments.erl:741-835) -- "major compaction" below.
+ * segment (src/ra_log_segment.erl:736-790, 819-908; src/ra_log_segments.erl:741-835) -- "major compaction" below --
+ * the mem-table flush, the batched reads, and the snapshot family as ragged batches: spans with their own starting
+ * values, the snapshot.dat / indexes images and their validation -- "snapshots and checkpoints" below.
  *
  * The arithmetic.  With a ZERO register and no final xor the CRC is linear over GF(2): raw(M) = M(x) * x^32 mod P,
  *     raw(A ++ B) = raw(A) * x^(8 |B|)  xor  raw(B),        raw(zeros ++ M) = raw(M)
@@ -155,7 +157,7 @@ __device__ __forceinline__ void shift_up(u64 &lo, u64 &hi, u32 sh) {
 /* Slot t of a payload of `len` >= 16 bytes at `pay`, `pad` zero bytes thought in front: the slot covers payload bytes
  * [p, p + 16), p = 16 t - pad.  COPY: the bytes also go to dst + p (the first, partial slot stores [0, 16): the bytes
  * it shares with its successor are written twice with the same value).  `fold` is xored into payload bytes 0..3. */
-template <bool COPY>
+template <bool COPY, int USER = 0>
 __device__ __forceinline__ uint4 load_slot(const unsigned char *pay, unsigned char *dst, u32 t, u32 pad, u32 fold) {
   const long long p = (long long)t * 16 - (long long)pad;
   if (p <= -16) return make_uint4(0, 0, 0, 0);
@@ -180,9 +182,10 @@ __device__ __forceinline__ uint4 load_slot(const unsigned char *pay, unsigned ch
   return v;
 }
 
-/* This lane's share of raw(fold-ed payload), already moved to the end of the payload: the xor over the GROUP lanes
+/* USER (here and in load_slot): a caller that wants instantiations of its own, see SNAP_USER.
+ * This lane's share of raw(fold-ed payload), already moved to the end of the payload: the xor over the GROUP lanes
  * is the raw value.  len >= 16 or len == 0 (nothing to do); every lane of the group makes the same number of rounds. */
-template <int GROUP, int UNROLL, bool COPY>
+template <int GROUP, int UNROLL, bool COPY, int USER = 0>
 __device__ __forceinline__ u32 lane_raw(const u32 *lds, const unsigned char *pay, unsigned char *dst, u32 len,
                                         u32 lane, u32 fold) {
   const u32 slots = (u32)(((u64)len + 15u) >> 4);
@@ -194,7 +197,7 @@ __device__ __forceinline__ u32 lane_raw(const u32 *lds, const unsigned char *pay
 #pragma unroll
     for (int k = 0; k < UNROLL; ++k) {
       v[k] = make_uint4(0, 0, 0, 0);
-      if (r0 + (u32)k < rounds) v[k] = load_slot<COPY>(pay, dst, (r0 + (u32)k) * GROUP + lane, pad, fold);
+      if (r0 + (u32)k < rounds) v[k] = load_slot<COPY, USER>(pay, dst, (r0 + (u32)k) * GROUP + lane, pad, fold);
     }
 #pragma unroll
     for (int k = 0; k < UNROLL; ++k)
@@ -1284,6 +1287,214 @@ __global__ __launch_bounds__(THREADS) void rgb_flush_copy_kernel(
   }
 }
 
+/* ---- snapshots and checkpoints (include/ra_gpu_wal.h, "snapshots and checkpoints") -----------------------
+ * A ragged batch: what an item checksums is a STREAM of up to two pieces at unrelated addresses, A ++ B, behind a
+ * starting value `head` (in raw terms: head is multiplied by x^(8 |A ++ B|)):
+ *     span      B = the span,                head = ~init
+ *     image     A = Meta, B = Data,          head = raw(<<MetaSize:32>> xor 0xFFFFFFFF)    (indexes: B = Data, 0xFFFFFFFF)
+ *     file      B = the bytes behind byte 9, head = 0xFFFFFFFF
+ * The host knows every size, so it plans the call (snap_plan, below) and the device only walks the plan:
+ *   group    a piece under SNAP_TBLOCK bytes gets 8, 16 or 64 lanes, as an entry of the per-entry kernel, one launch
+ *            per width; the head of the stream is folded into the first four bytes of its first piece
+ *   block    a longer piece is cut into blocks of SNAP_BLOCK bytes aligned to its END; the blocks of all such pieces
+ *            are numbered through and dealt to one capped grid, a workgroup per block, the piece found by bisection
+ *   finish   per item: raw(A), raw(B) joined (a workgroup for an item of several blocks, a lane for every other), then what
+ *            the call is about -- the span's CRC, the image's header, the file's info row
+ * Each pass is its own launch, so no workgroup ever waits for another.  A span that is one group piece needs no finish:
+ * its group writes the CRC.  The kernels' parameter types are the unit's own (see "major compaction" above). */
+constexpr u32 SNAP_BLOCK = STREAM_BLOCK;
+constexpr u32 SNAP_T8 = 320u, SNAP_T16 = 1024u;      /* 8 lanes up to 320 bytes, 16 under 1 KiB, as group_width() */
+constexpr u32 SNAP_TBLOCK = 16384u;                   /* a wavefront under 16 KiB, blocks from there */
+constexpr u32 SNAP_DIRECT = 0x80000000u;              /* piece.slot: the CRC goes straight to crcs[slot & ~SNAP_DIRECT] */
+constexpr int SNAP_SPANS = 0, SNAP_BUILD = 1, SNAP_VALIDATE = 2;
+/* lane_raw / load_slot of their own for these kernels: the same source, but the other kernels' instantiations see the
+ * starting values they always saw (constants), and so compile to what they compiled to before */
+constexpr int SNAP_USER = 1;
+
+struct snap_piece { u64 src, len, dst; u32 fold, slot; };                                  /* staged from the host */
+struct snap_item { u64 off, len_a, len_b; u32 slot_a, slot_b, nblk_a, nblk_b, head, kind; };
+struct snap_row { u32 status, version, stored_crc, computed_crc; u64 meta_offset; u32 meta_len, _pad; u64 data_offset, data_bytes; };
+static_assert(sizeof(snap_piece) == 32 && sizeof(snap_item) == 48 && sizeof(snap_row) == sizeof(rgb_snap_info), "");
+
+/* pow8[k] = x^(8 2^k): x^(8 n) is the product over the set bits of n */
+struct Pow8 { u32 v[64]; };
+constexpr Pow8 make_pow8() {
+  Pow8 t{};
+  u32 sq = X0 >> 8;
+  for (int k = 0; k < 64; ++k) { t.v[k] = sq; sq = mulmod_c(sq, sq); }
+  return t;
+}
+__device__ const Pow8 g_pow8 = make_pow8();
+__device__ __forceinline__ u32 xpow8(u64 n) {
+  u32 p = X0;
+  for (int k = 0; n; ++k, n >>= 1)
+    if (n & 1u) p = mulmod(p, g_pow8.v[k]);
+  return p;
+}
+
+/* raws[slot] = raw(piece, its first four bytes xored with fold) = raw(piece) ^ fold * x^(8 len), for the n pieces of
+ * one width; COPY: the piece goes to out + dst as it is read */
+template <int GROUP, bool COPY>
+__global__ __launch_bounds__(THREADS) void rgb_snap_group_kernel(const snap_piece *__restrict__ pieces, u32 n,
+                                                                 const unsigned char *__restrict__ data,
+                                                                 unsigned char *__restrict__ out, u32 *__restrict__ raws,
+                                                                 u32 *__restrict__ crcs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[LDS_WORDS];
+  load_tables<GROUP>(lds);
+  constexpr u32 PER_BLOCK = THREADS / GROUP;
+  constexpr int UNROLL = GROUP == 64 ? 4 : 2;
+  const u32 lane = threadIdx.x & (GROUP - 1);
+  for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
+    const u32 e = base + threadIdx.x / GROUP;
+    const bool live = e < n;
+    snap_piece p;
+    p.src = p.len = p.dst = 0ull; p.fold = p.slot = 0u;
+    if (live) p = pieces[e];
+    const u32 len = (u32)p.len;                         /* < SNAP_TBLOCK */
+    const unsigned char *pay = data + p.src;
+    unsigned char *dst = COPY ? out + p.dst : nullptr;
+    const u32 part = lane_raw<GROUP, UNROLL, COPY, SNAP_USER>(lds, pay, dst, live && len >= 16u ? len : 0u, lane, p.fold);
+    u32 raw = group_xor<GROUP>(part);
+    if (live && lane == 0u) {
+      if (len < 16u) raw = ~crc_bytes(lds, ~p.fold, pay, len, dst);
+      if (p.slot & SNAP_DIRECT) crcs[p.slot & ~SNAP_DIRECT] = ~raw;
+      else raws[p.slot] = raw;
+    }
+  }
+}
+
+/* raws[slot + b] = raw(block b of its piece), for the n_blocks blocks of the n_big long pieces: blk_start[j] = the
+ * number of the first block of piece j, blk_start[n_big] = n_blocks.  As rgb_seg_stream_kernel: the first block of a
+ * piece is the short one. */
+template <bool COPY>
+__global__ __launch_bounds__(THREADS) void rgb_snap_block_kernel(const snap_piece *__restrict__ pieces,
+                                                                 const u32 *__restrict__ blk_start, u32 n_big, u32 n_blocks,
+                                                                 const unsigned char *__restrict__ data,
+                                                                 unsigned char *__restrict__ out, u32 *__restrict__ raws) {
+  __shared__ __attribute__((aligned(16))) u32 lds[LDS_WORDS];
+  __shared__ u32 red[THREADS / 64];
+  load_tables<256>(lds);
+  for (u32 gb = blockIdx.x; gb < n_blocks; gb += gridDim.x) {
+    u32 lo = 0, hi = n_big;                             /* the last piece whose first block is <= gb */
+    while (hi - lo > 1u) {
+      const u32 mid = (lo + hi) >> 1;
+      if (blk_start[mid] <= gb) lo = mid; else hi = mid;
+    }
+    const snap_piece p = pieces[lo];
+    const u32 b = gb - blk_start[lo], nb = blk_start[lo + 1u] - blk_start[lo];
+    const u64 first_len = p.len - (u64)(nb - 1u) * SNAP_BLOCK;             /* 1 .. SNAP_BLOCK */
+    const u64 start = b ? first_len + (u64)(b - 1u) * SNAP_BLOCK : 0ull;
+    const u32 len = b ? SNAP_BLOCK : (u32)first_len;
+    /* a first block under 16 bytes: its one slot loads (and copies) [0, 16) of the piece, and keeps its own bytes */
+    const u32 part = lane_raw<256, 4, COPY, SNAP_USER>(lds, data + p.src + start, COPY ? out + p.dst + start : nullptr, len,
+                                            threadIdx.x, 0u);
+    const u32 w = group_xor<64>(part);
+    if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0u) raws[p.slot + b] = red[0] ^ red[1] ^ red[2] ^ red[3];
+    __syncthreads();
+  }
+}
+
+/* raw(piece) from its blocks' values, by the whole workgroup (every lane comes here and gets the answer): the sum of
+ * rgb_seg_combine_kernel -- rounds of THREADS blocks, a round is x^(8 SNAP_BLOCK THREADS) */
+__device__ __forceinline__ u32 snap_join_blocks(const u32 *__restrict__ partials, u32 n_blocks, u32 *red) {
+  u32 acc = 0;
+  const u32 k_round = g_tab.blk[256];
+  for (u32 b = threadIdx.x; b < n_blocks; b += THREADS) acc = mulmod(acc, k_round) ^ partials[b];
+  if (threadIdx.x < n_blocks) {
+    const u32 last = threadIdx.x + ((n_blocks - 1u - threadIdx.x) / THREADS) * THREADS;
+    acc = mulmod(acc, g_tab.blk[n_blocks - 1u - last]);
+  }
+  const u32 w = group_xor<64>(acc);
+  if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  const u32 raw = red[0] ^ red[1] ^ red[2] ^ red[3];
+  __syncthreads();
+  return raw;
+}
+
+__device__ __forceinline__ void put_be32(unsigned char *at, u32 v) {
+  at[0] = (unsigned char)(v >> 24); at[1] = (unsigned char)(v >> 16); at[2] = (unsigned char)(v >> 8); at[3] = (unsigned char)v;
+}
+
+/* recover/1, validate/2, parse_snapshot/1 and read_meta_internal/1 of one file, whose CRC (behind byte 9) is `crc` */
+__device__ __forceinline__ snap_row snap_check_file(const unsigned char *f, u64 off, u64 n, u32 kind, bool meta_only, u32 crc) {
+  snap_row r{};
+  const bool snapshot = kind == RGB_SNAP_KIND_SNAPSHOT;
+  if (meta_only && n == 0ull) { r.status = RGB_SNAP_EOF; return r; }
+  if (n < RGB_SNAP_HEADER_BYTES || f[0] != 'R' || f[1] != 'A' || f[2] != 'S' || f[3] != (snapshot ? 'N' : 'I')) {
+    r.status = RGB_SNAP_INVALID_FORMAT;
+    return r;
+  }
+  r.version = f[4];
+  r.stored_crc = ld_be32(f + 5);
+  if (r.version != 1u || (meta_only && snapshot && n < RGB_SNAP_META_HEADER_BYTES)) { r.status = RGB_SNAP_INVALID_VERSION; return r; }
+  if (!meta_only) {
+    r.computed_crc = crc;
+    if (crc != r.stored_crc) { r.status = RGB_SNAP_CHECKSUM; return r; }
+  }
+  if (!snapshot) {
+    r.data_offset = off + RGB_SNAP_HEADER_BYTES; r.data_bytes = n - RGB_SNAP_HEADER_BYTES;
+    return r;
+  }
+  if (n < RGB_SNAP_META_HEADER_BYTES) { r.status = RGB_SNAP_BAD_META; return r; }
+  const u32 meta_size = ld_be32(f + RGB_SNAP_HEADER_BYTES);
+  if (meta_size > n - RGB_SNAP_META_HEADER_BYTES) { r.status = RGB_SNAP_BAD_META; return r; }
+  r.meta_offset = off + RGB_SNAP_META_HEADER_BYTES; r.meta_len = meta_size;
+  r.data_offset = r.meta_offset + meta_size; r.data_bytes = n - RGB_SNAP_META_HEADER_BYTES - meta_size;
+  return r;
+}
+
+/* item i, its pieces' raw values known: raw(stream) = (head x^(8 |A|) ^ raw(A)) x^(8 |B|) ^ raw(B) */
+template <int MODE>
+__device__ __forceinline__ void snap_finish_item(const snap_item &it, u32 i, u32 raw_a, u32 raw_b,
+                                                 const unsigned char *__restrict__ data, unsigned char *__restrict__ out,
+                                                 u32 *__restrict__ crcs, snap_row *__restrict__ rows) {
+  u32 t = raw_a;
+  if (it.head) t ^= mulmod(it.head, xpow8(MODE == SNAP_VALIDATE ? 0ull : it.len_a));   /* a file has no piece A */
+  u32 raw = raw_b;
+  if (t) raw ^= mulmod(t, xpow8(it.len_b));
+  const u32 crc = ~raw;
+  if (MODE == SNAP_SPANS) {
+    crcs[it.off] = crc;
+  } else if (MODE == SNAP_BUILD) {
+    unsigned char *o = out + it.off;
+    const bool snapshot = it.kind == RGB_SNAP_KIND_SNAPSHOT;
+    o[0] = 'R'; o[1] = 'A'; o[2] = 'S'; o[3] = snapshot ? 'N' : 'I'; o[4] = 1;
+    put_be32(o + 5, crc);
+    if (snapshot) put_be32(o + RGB_SNAP_HEADER_BYTES, (u32)it.len_a);
+    if (crcs) crcs[i] = crc;
+  } else {
+    /* len_a = the file's n_bytes (it has no piece A) */
+    rows[i] = snap_check_file(data + it.off, it.off, it.len_a, it.kind & 0xFFu, (it.kind >> 8) & RGB_SNAP_META_ONLY, crc);
+  }
+}
+
+/* `big` = the n_big items that have a piece of more than one block, a workgroup each; then every other item, a lane each
+ * (the items of a spans call are its long spans only: the others are DIRECT pieces) */
+template <int MODE>
+__global__ __launch_bounds__(THREADS) void rgb_snap_finish_kernel(const snap_item *__restrict__ items, u32 n_items,
+                                                                  const u32 *__restrict__ big, u32 n_big,
+                                                                  const u32 *__restrict__ raws,
+                                                                  const unsigned char *__restrict__ data,
+                                                                  unsigned char *__restrict__ out, u32 *__restrict__ crcs,
+                                                                  snap_row *__restrict__ rows) {
+  __shared__ u32 red[THREADS / 64];
+  for (u32 k = blockIdx.x; k < n_big; k += gridDim.x) {
+    const u32 i = big[k];
+    const snap_item it = items[i];
+    const u32 raw_a = snap_join_blocks(raws + it.slot_a, it.nblk_a, red);
+    const u32 raw_b = snap_join_blocks(raws + it.slot_b, it.nblk_b, red);
+    if (threadIdx.x == 0u) snap_finish_item<MODE>(it, i, raw_a, raw_b, data, out, crcs, rows);
+  }
+  for (u32 i = blockIdx.x * THREADS + threadIdx.x; i < n_items; i += gridDim.x * THREADS) {
+    const snap_item it = items[i];
+    if (it.nblk_a > 1u || it.nblk_b > 1u) continue;
+    snap_finish_item<MODE>(it, i, it.nblk_a ? raws[it.slot_a] : 0u, it.nblk_b ? raws[it.slot_b] : 0u, data, out, crcs, rows);
+  }
+}
+
 /* x^(8 n) mod P on the host */
 inline u32 host_xpow8(u64 n) { return xpow8_c(n); }
 
@@ -1381,6 +1592,11 @@ struct stage {
   dev_buf partials;                                   /* STREAM_MAX_BLOCKS values + the one result of the host-buffer form */
   pinned_upload compact_desc, flush_writers, read_desc;   /* device forms: the host arrays of a call ... */
   dev_buf compact_work, flush_work, read_work;        /* ... and its scratch plan */
+  pinned_upload snap_plan_up;                         /* snapshots and checkpoints: the plan of a call ... */
+  dev_buf snap_raws, infos;                           /* ... its pieces' raw values; the rows of the host-buffer form */
+  std::vector<snap_piece> snap_pieces;                /* the plan on the host, before it is sorted into the upload */
+  std::vector<snap_item> snap_items;
+  std::vector<u32> snap_big;
 };
 std::recursive_mutex g_mu;     /* the host-buffer forms call the device forms with it held */
 /* never destroyed: a context that is still open when the process ends must not free through a runtime that is gone */
@@ -2004,4 +2220,259 @@ extern "C" int rgb_segment_read(rgb_ctx *ctx, const rgb_seg_read_source *sources
   if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
   *total = t;
   return RGB_OK;
+}
+
+/* ---- snapshots and checkpoints: ragged CRC batches, images, validation ---------------------------------- */
+
+extern "C" int rgb_snapshot_spans_check(const rgb_crc_span *spans, uint32_t n, uint64_t data_bytes, uint64_t *sum_bytes);
+extern "C" int rgb_snapshot_build_check(const rgb_snap_item *items, uint32_t n, uint64_t data_bytes, uint64_t out_bytes,
+                                        uint64_t *sum_bytes);
+extern "C" int rgb_snapshot_files_check(const rgb_snap_file *files, uint32_t n, uint64_t files_bytes, uint64_t *sum_bytes);
+
+namespace {
+namespace seg {
+
+/* the pass that takes a piece: 8, 16 or 64 lanes, or blocks */
+inline int snap_tier(u64 len) { return len <= SNAP_T8 ? 0 : len < SNAP_T16 ? 1 : len < SNAP_TBLOCK ? 2 : 3; }
+
+/* erlang:crc32(<<V:32>>) before its final xor: raw(<<V:32>> xor 0xFFFFFFFF), the head of an image's stream */
+inline u32 snap_head_of_be32(u32 v) {
+  u32 crc = 0xFFFFFFFFu;
+  for (int k = 3; k >= 0; --k) {
+    crc ^= (v >> (8 * k)) & 0xFFu;
+    for (int b = 0; b < 8; ++b) crc = (crc & 1u) ? (crc >> 1) ^ POLY : crc >> 1;
+  }
+  return crc;
+}
+
+/* The plan of one call, built on the host (in the context's vectors), sorted by pass into the pinned block and sent up:
+ *   [ pieces: 8 lanes | 16 | 64 | blocks ] [ blk_start: a value per long piece, and the total ] [ items ] [ big ] */
+struct snap_plan {
+  stage &s;
+  u64 slots = 0, blocks = 0;                            /* raw values / blocks the call leaves */
+  u32 count[4] = {0u, 0u, 0u, 0u};
+  bool too_large = false;
+  explicit snap_plan(stage &st) : s(st) { s.snap_pieces.clear(); s.snap_items.clear(); s.snap_big.clear(); }
+
+  /* one piece -> the raw values it leaves, from *slot on; `direct`: SNAP_DIRECT | the span a group piece answers */
+  u32 piece(u64 src, u64 len, u64 dst, u32 fold, u32 direct, u32 *slot) {
+    const int t = snap_tier(len);
+    snap_piece p;
+    p.src = src; p.len = len; p.dst = dst; p.fold = fold; p.slot = direct;
+    u64 n_raw = 1;
+    if (!direct) {
+      if (t == 3) { n_raw = (len + SNAP_BLOCK - 1u) / SNAP_BLOCK; blocks += n_raw; }
+      if (n_raw > 0x7FFFFFFFull || slots + n_raw > 0x7FFFFFFFull) { too_large = true; n_raw = 1; }
+      p.slot = (u32)slots;
+      slots += n_raw;
+    }
+    if (slot) *slot = p.slot;
+    count[t] += 1u;
+    s.snap_pieces.push_back(p);
+    return (u32)n_raw;
+  }
+  /* item `it` (off and kind are the caller's) checksums A ++ B behind `head`: the head goes into the stream's first
+   * piece when that is a group piece, and stays with the item otherwise */
+  void stream(snap_item it, u64 a_src, u64 a_len, u64 a_dst, u64 b_src, u64 b_len, u64 b_dst, u32 head) {
+    it.len_a = a_len; it.len_b = b_len; it.head = head;
+    it.slot_a = it.slot_b = it.nblk_a = it.nblk_b = 0u;
+    if (a_len) {
+      const bool folds = snap_tier(a_len) < 3;
+      it.nblk_a = piece(a_src, a_len, a_dst, folds ? head : 0u, 0u, &it.slot_a);
+      if (folds) it.head = 0u;
+    }
+    if (b_len) {
+      const bool folds = !a_len && snap_tier(b_len) < 3;
+      it.nblk_b = piece(b_src, b_len, b_dst, folds ? head : 0u, 0u, &it.slot_b);
+      if (folds) it.head = 0u;
+    }
+    if (it.nblk_a > 1u || it.nblk_b > 1u) s.snap_big.push_back((u32)s.snap_items.size());
+    s.snap_items.push_back(it);
+  }
+
+  /* Upload and run: the group and block passes, then finish<MODE> (COPY with SNAP_BUILD).  Nothing is enqueued unless
+   * the plan fits. */
+  template <int MODE>
+  int run(const void *d_data, void *d_out, void *d_crcs, void *d_rows, hipStream_t st) {
+    constexpr bool COPY = MODE == SNAP_BUILD;
+    if (too_large) return RGB_E_NOMEM;
+    const size_t n_pieces = s.snap_pieces.size(), n_items = s.snap_items.size(), n_big = s.snap_big.size();
+    if (!n_pieces && !n_items) return RGB_OK;
+    const size_t off_blk = n_pieces * sizeof(snap_piece);
+    const size_t off_items = up16(off_blk + ((size_t)count[3] + 1u) * 4u);
+    const size_t off_big = off_items + n_items * sizeof(snap_item);
+    const size_t need = off_big + n_big * 4u + 16u;
+    pinned_upload &up = s.snap_plan_up;
+    int rc;
+    if ((rc = up.prepare(need))) return rc;
+    unsigned char *h = (unsigned char *)up.h;
+    snap_piece *h_pieces = (snap_piece *)h;
+    u32 *h_blk = (u32 *)(h + off_blk);
+    u32 first[4], at[4];
+    first[0] = 0u;
+    for (int t = 1; t < 4; ++t) first[t] = first[t - 1] + count[t - 1];
+    for (int t = 0; t < 4; ++t) at[t] = first[t];
+    u32 blk = 0;
+    for (const snap_piece &p : s.snap_pieces) {
+      const int t = snap_tier(p.len);
+      if (t == 3) { h_blk[at[3] - first[3]] = blk; blk += (u32)((p.len + SNAP_BLOCK - 1u) / SNAP_BLOCK); }
+      h_pieces[at[t]++] = p;
+    }
+    h_blk[count[3]] = blk;
+    if (n_items) memcpy(h + off_items, s.snap_items.data(), n_items * sizeof(snap_item));
+    if (n_big) memcpy(h + off_big, s.snap_big.data(), n_big * 4u);
+    if (s.snap_raws.reserve((size_t)slots * 4u + 16u)) return RGB_E_NOMEM;
+    if ((rc = up.upload(need, st))) return rc;
+    const unsigned char *d = (const unsigned char *)up.d.p;
+    const snap_piece *d_pieces = (const snap_piece *)d;
+    const unsigned char *data = (const unsigned char *)d_data;
+    unsigned char *out = (unsigned char *)d_out;
+    u32 *raws = (u32 *)s.snap_raws.p, *crcs = (u32 *)d_crcs;
+    (void)hipGetLastError();
+    const u32 widths[3] = {8u, 16u, 64u};
+    for (int t = 0; t < 3; ++t) {
+      if (!count[t]) continue;
+      with_width(widths[t], [&](auto g) {
+        hipLaunchKernelGGL((rgb_snap_group_kernel<decltype(g)::value, COPY>), dim3(entry_grid(count[t], widths[t])),
+                           dim3(THREADS), 0, st, d_pieces + first[t], count[t], data, out, raws, crcs);
+      });
+    }
+    if (count[3])
+      hipLaunchKernelGGL(rgb_snap_block_kernel<COPY>, dim3(blk < GRID_CAP ? blk : GRID_CAP), dim3(THREADS), 0, st,
+                         d_pieces + first[3], (const u32 *)(d + off_blk), count[3], blk, data, out, raws);
+    const size_t by_lane = (n_items + THREADS - 1u) / THREADS;
+    const size_t grid = n_big > by_lane ? n_big : by_lane;
+    if (grid)
+      hipLaunchKernelGGL(rgb_snap_finish_kernel<MODE>, dim3((u32)(grid < GRID_CAP ? grid : GRID_CAP)), dim3(THREADS), 0, st,
+                         (const snap_item *)(d + off_items), (u32)n_items, (const u32 *)(d + off_big), (u32)n_big,
+                         (const u32 *)raws, data, out, crcs, (snap_row *)d_rows);
+    return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+  }
+};
+
+inline snap_item snap_item_of(u64 off, u32 kind) {
+  snap_item it;
+  memset(&it, 0, sizeof it);
+  it.off = off; it.kind = kind;
+  return it;
+}
+}  // namespace seg
+}  // namespace
+
+extern "C" int rgb_crc32_spans_device(rgb_ctx *ctx, const rgb_crc_span *spans, uint32_t n, const void *d_data,
+                                      uint64_t data_bytes, void *d_crcs, void *stream) {
+  if (!ctx || (n && (!spans || !d_crcs)) || (data_bytes && !d_data)) return RGB_E_INVAL;
+  if (int rc = rgb_snapshot_spans_check(spans, n, data_bytes, nullptr)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::snap_plan plan(seg::g_stages[ctx]);
+  for (uint32_t i = 0; i < n; ++i) {
+    const rgb_crc_span &sp = spans[i];
+    if (seg::snap_tier(sp.n_bytes) < 3) plan.piece(sp.offset, sp.n_bytes, 0u, ~sp.init, seg::SNAP_DIRECT | i, nullptr);
+    else plan.stream(seg::snap_item_of(i, 0u), 0u, 0u, 0u, sp.offset, sp.n_bytes, 0u, ~sp.init);
+  }
+  return plan.run<seg::SNAP_SPANS>(d_data, nullptr, d_crcs, nullptr, st);
+}
+
+extern "C" int rgb_snapshot_build_device(rgb_ctx *ctx, const rgb_snap_item *items, uint32_t n, const void *d_data,
+                                         uint64_t data_bytes, void *d_out, uint64_t out_bytes, void *d_crcs, void *stream) {
+  if (!ctx || (n && (!items || !d_out)) || (data_bytes && !d_data)) return RGB_E_INVAL;
+  if (int rc = rgb_snapshot_build_check(items, n, data_bytes, out_bytes, nullptr)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::snap_plan plan(seg::g_stages[ctx]);
+  for (uint32_t i = 0; i < n; ++i) {
+    const rgb_snap_item &it = items[i];
+    if (it.kind == RGB_SNAP_KIND_SNAPSHOT) {
+      const uint64_t meta_at = it.out_offset + RGB_SNAP_META_HEADER_BYTES;
+      plan.stream(seg::snap_item_of(it.out_offset, it.kind), it.meta_offset, it.meta_len, meta_at, it.data_offset,
+                  it.data_bytes, meta_at + it.meta_len, seg::snap_head_of_be32(it.meta_len));
+    } else {
+      plan.stream(seg::snap_item_of(it.out_offset, it.kind), 0u, 0u, 0u, it.data_offset, it.data_bytes,
+                  it.out_offset + RGB_SNAP_HEADER_BYTES, 0xFFFFFFFFu);
+    }
+  }
+  return plan.run<seg::SNAP_BUILD>(d_data, d_out, d_crcs, nullptr, st);
+}
+
+extern "C" int rgb_snapshot_validate_device(rgb_ctx *ctx, const rgb_snap_file *files, uint32_t n, const void *d_files,
+                                            uint64_t files_bytes, void *d_infos, void *stream) {
+  if (!ctx || (n && (!files || !d_infos)) || (files_bytes && !d_files)) return RGB_E_INVAL;
+  if (int rc = rgb_snapshot_files_check(files, n, files_bytes, nullptr)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::snap_plan plan(seg::g_stages[ctx]);
+  for (uint32_t i = 0; i < n; ++i) {
+    const rgb_snap_file &f = files[i];
+    const bool sums = !(f.flags & RGB_SNAP_META_ONLY) && f.n_bytes > RGB_SNAP_HEADER_BYTES;
+    seg::snap_item it = seg::snap_item_of(f.offset, f.kind | (f.flags << 8));
+    /* the item has no piece A: len_a carries the file's size to the finish pass */
+    plan.stream(it, 0u, 0u, 0u, f.offset + RGB_SNAP_HEADER_BYTES, sums ? f.n_bytes - RGB_SNAP_HEADER_BYTES : 0u, 0u,
+                0xFFFFFFFFu);
+    plan.s.snap_items.back().len_a = f.n_bytes;
+  }
+  return plan.run<seg::SNAP_VALIDATE>(d_files, nullptr, nullptr, d_infos, st);
+}
+
+extern "C" int rgb_crc32_spans(rgb_ctx *ctx, const rgb_crc_span *spans, uint32_t n, const void *data, uint64_t data_bytes,
+                               uint32_t *crcs) {
+  if (!ctx || (n && (!spans || !crcs)) || (data_bytes && !data)) return RGB_E_INVAL;
+  if (int rc = rgb_snapshot_spans_check(spans, n, data_bytes, nullptr)) return rc;
+  if (n == 0) return RGB_OK;
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (s.crcs.reserve((size_t)n * 4u)) return RGB_E_NOMEM;
+  int rc;
+  if ((rc = seg::stage_in(s.data, data, (size_t)data_bytes, st))) return rc;
+  if ((rc = rgb_crc32_spans_device(ctx, spans, n, s.data.p, data_bytes, s.crcs.p, st))) return rc;
+  return seg::fetch(crcs, s.crcs, (size_t)n * 4u, st);
+}
+
+extern "C" int rgb_snapshot_build(rgb_ctx *ctx, const rgb_snap_item *items, uint32_t n, const void *data,
+                                  uint64_t data_bytes, void *out, uint64_t out_bytes, uint32_t *crcs) {
+  if (!ctx || (n && (!items || !out)) || (data_bytes && !data)) return RGB_E_INVAL;
+  uint64_t sum = 0;
+  if (int rc = rgb_snapshot_build_check(items, n, data_bytes, out_bytes, &sum)) return rc;
+  if (n == 0) return RGB_OK;
+  /* the images are packed on the device in the caller's order, wherever they go in `out` */
+  std::vector<rgb_snap_item> packed(items, items + n);
+  const uint64_t total = rgb_snapshot_layout(packed.data(), n, 0u);
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (s.out.reserve((size_t)total) || s.crcs.reserve((size_t)n * 4u)) return RGB_E_NOMEM;
+  int rc;
+  if ((rc = seg::stage_in(s.data, data, (size_t)data_bytes, st))) return rc;
+  if ((rc = rgb_snapshot_build_device(ctx, packed.data(), n, s.data.p, data_bytes, s.out.p, total, s.crcs.p, st))) return rc;
+  /* only the images' own bytes come back: neighbours in `out` in one copy */
+  for (uint32_t i = 0; i < n;) {
+    const uint64_t from = packed[i].out_offset, to = items[i].out_offset;
+    uint64_t bytes = 0;
+    for (; i < n && items[i].out_offset == to + bytes; ++i)
+      bytes += (i + 1u < n ? packed[i + 1u].out_offset : total) - packed[i].out_offset;
+    if (bytes && hipMemcpyAsync((unsigned char *)out + to, (const unsigned char *)s.out.p + from, (size_t)bytes,
+                                hipMemcpyDeviceToHost, st) != hipSuccess)
+      return RGB_E_HIP;
+  }
+  if (crcs) return seg::fetch(crcs, s.crcs, (size_t)n * 4u, st);
+  return hipStreamSynchronize(st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_snapshot_validate(rgb_ctx *ctx, const rgb_snap_file *files, uint32_t n, const void *bytes,
+                                     uint64_t files_bytes, rgb_snap_info *infos) {
+  if (!ctx || (n && (!files || !infos)) || (files_bytes && !bytes)) return RGB_E_INVAL;
+  if (int rc = rgb_snapshot_files_check(files, n, files_bytes, nullptr)) return rc;
+  if (n == 0) return RGB_OK;
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  if (s.infos.reserve((size_t)n * sizeof(rgb_snap_info))) return RGB_E_NOMEM;
+  int rc;
+  if ((rc = seg::stage_in(s.data, bytes, (size_t)files_bytes, st))) return rc;
+  if ((rc = rgb_snapshot_validate_device(ctx, files, n, s.data.p, files_bytes, s.infos.p, st))) return rc;
+  return seg::fetch(infos, s.infos, (size_t)n * sizeof(rgb_snap_info), st);
 }

@@ -1,11 +1,12 @@
 /*
  * rgb_segment_host.cpp -- the host-only half of the segment part of include/ra_gpu_wal.h: the file layout and the
  * index walk of a segment file (src/ra_log_segment.erl:1118-1138, 1197-1219), and the descriptor checks of a compaction
- * group, of a mem-table flush and of a batched read.  No HIP here, so the file also builds on its own under the
- * sanitizers (tests/test_segment.py::test_segment_scan_under_sanitizers,
+ * group, of a mem-table flush, of a batched read and of the snapshot calls.  No HIP here, so the file also builds on
+ * its own under the sanitizers (tests/test_segment.py::test_segment_scan_under_sanitizers,
  * tests/test_segment_compact.py::test_compact_descriptors_under_sanitizers,
  * tests/test_segment_flush.py::test_flush_descriptors_under_sanitizers,
- * tests/test_segment_read.py::test_read_descriptors_under_sanitizers).
+ * tests/test_segment_read.py::test_read_descriptors_under_sanitizers,
+ * tests/test_snapshot_files.py::test_snapshot_descriptors_under_sanitizers).
  */
 #include <stdint.h>
 #include "../../include/ra_gpu_wal.h"
@@ -145,6 +146,78 @@ extern "C" int rgb_seg_read_check(const rgb_seg_read_source *sources, uint32_t n
   if (covered) *covered = (uint32_t)named;                         /* <= n_req: the slices are disjoint */
   if (sum_bytes) *sum_bytes = sum;
   if (out_bound) *out_bound = bound;
+  return RGB_OK;
+}
+
+/* ---- snapshots and checkpoints: the descriptors of a call, checked before anything is enqueued -------------
+ * Library-internal (rgb_segment.hip calls them; not in the header).  *sum_bytes = the bytes the call checksums
+ * (saturating). */
+#define RGB_SNAP_MAX_ITEMS 0x7FFFFFFFu
+
+static inline bool snap_inside(uint64_t offset, uint64_t n_bytes, uint64_t buffer_bytes) {
+  return offset <= buffer_bytes && n_bytes <= buffer_bytes - offset;
+}
+static inline uint64_t snap_sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
+
+extern "C" int rgb_snapshot_spans_check(const rgb_crc_span *spans, uint32_t n, uint64_t data_bytes, uint64_t *sum_bytes) {
+  if (n > RGB_SNAP_MAX_ITEMS || (n && !spans)) return RGB_E_INVAL;
+  uint64_t sum = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!snap_inside(spans[i].offset, spans[i].n_bytes, data_bytes)) return RGB_E_INVAL;
+    sum = snap_sat_add(sum, spans[i].n_bytes);
+  }
+  if (sum_bytes) *sum_bytes = sum;
+  return RGB_OK;
+}
+
+/* the bytes of one image; 0 and *ok = false when the sum does not fit 64 bits */
+static inline uint64_t snap_image_bytes(const rgb_snap_item &it, bool *ok) {
+  const uint64_t head = it.kind == RGB_SNAP_KIND_SNAPSHOT ? RGB_SNAP_META_HEADER_BYTES : RGB_SNAP_HEADER_BYTES;
+  const uint64_t size = head + it.meta_len + it.data_bytes;
+  *ok = size >= it.data_bytes;
+  return *ok ? size : 0u;
+}
+
+extern "C" uint64_t rgb_snapshot_layout(rgb_snap_item *items, uint32_t n, uint64_t base) {
+  uint64_t pos = base;
+  for (uint32_t i = 0; i < n; ++i) {
+    bool ok;
+    items[i].out_offset = pos;
+    pos += snap_image_bytes(items[i], &ok);
+  }
+  return pos;
+}
+
+extern "C" int rgb_snapshot_build_check(const rgb_snap_item *items, uint32_t n, uint64_t data_bytes, uint64_t out_bytes,
+                                        uint64_t *sum_bytes) {
+  if (n > RGB_SNAP_MAX_ITEMS || (n && !items)) return RGB_E_INVAL;
+  uint64_t sum = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const rgb_snap_item &it = items[i];
+    if (it.kind != RGB_SNAP_KIND_SNAPSHOT && it.kind != RGB_SNAP_KIND_INDEXES) return RGB_E_INVAL;
+    if (it.kind == RGB_SNAP_KIND_INDEXES && it.meta_len != 0u) return RGB_E_INVAL;
+    if (!snap_inside(it.meta_offset, it.meta_len, data_bytes)) return RGB_E_INVAL;
+    if (!snap_inside(it.data_offset, it.data_bytes, data_bytes)) return RGB_E_INVAL;
+    bool ok;
+    const uint64_t size = snap_image_bytes(it, &ok);
+    if (!ok || !snap_inside(it.out_offset, size, out_bytes)) return RGB_E_INVAL;
+    sum = snap_sat_add(sum, size);
+  }
+  if (sum_bytes) *sum_bytes = sum;
+  return RGB_OK;
+}
+
+extern "C" int rgb_snapshot_files_check(const rgb_snap_file *files, uint32_t n, uint64_t files_bytes, uint64_t *sum_bytes) {
+  if (n > RGB_SNAP_MAX_ITEMS || (n && !files)) return RGB_E_INVAL;
+  uint64_t sum = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const rgb_snap_file &f = files[i];
+    if (f.kind != RGB_SNAP_KIND_SNAPSHOT && f.kind != RGB_SNAP_KIND_INDEXES) return RGB_E_INVAL;
+    if (f.flags & ~RGB_SNAP_META_ONLY) return RGB_E_INVAL;
+    if (!snap_inside(f.offset, f.n_bytes, files_bytes)) return RGB_E_INVAL;
+    if (!(f.flags & RGB_SNAP_META_ONLY)) sum = snap_sat_add(sum, f.n_bytes);
+  }
+  if (sum_bytes) *sum_bytes = sum;
   return RGB_OK;
 }
 

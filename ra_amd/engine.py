@@ -49,7 +49,9 @@ WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "r
                "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate",
                "rgb_segment_compact_bound", "rgb_segment_info_device", "rgb_segment_info", "rgb_segment_compact_device",
                "rgb_segment_compact", "rgb_segment_flush_bound", "rgb_segment_flush_device", "rgb_segment_flush",
-               "rgb_segment_read_device", "rgb_segment_read"]                                                                                 # include/ra_gpu_wal.h
+               "rgb_segment_read_device", "rgb_segment_read",
+               "rgb_crc32_spans_device", "rgb_crc32_spans", "rgb_snapshot_layout", "rgb_snapshot_build_device",
+               "rgb_snapshot_build", "rgb_snapshot_validate_device", "rgb_snapshot_validate"]                                                                                 # include/ra_gpu_wal.h
 
 
 class RgbError(RuntimeError):
@@ -221,6 +223,14 @@ def lib():
     L.rgb_segment_flush.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp, C.c_uint64, vp]
     L.rgb_segment_read_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, u32, vp, vp, C.c_uint64, vp, vp, vp]
     L.rgb_segment_read.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, u32, vp, vp, C.c_uint64, vp, vp]
+    L.rgb_crc32_spans_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp]
+    L.rgb_crc32_spans.argtypes = [vp, vp, u32, vp, C.c_uint64, vp]
+    L.rgb_snapshot_layout.restype = C.c_uint64
+    L.rgb_snapshot_layout.argtypes = [vp, u32, C.c_uint64]
+    L.rgb_snapshot_build_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    L.rgb_snapshot_build.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64, vp]
+    L.rgb_snapshot_validate_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, vp]
+    L.rgb_snapshot_validate.argtypes = [vp, vp, u32, vp, C.c_uint64, vp]
     if L.rgb_abi_version() != abi.ABI_VERSION and not (os.environ.get("RGB_LIB") and L.rgb_abi_version() == abi.ABI_VERSION - 1):
         raise RuntimeError("ABI version mismatch")     # (RGB_LIB=<the previous ABI's build>: A/B timing, tools/ only)
     for i, dt in enumerate(abi.STRUCT_DTYPES):
@@ -791,6 +801,67 @@ class RaGpuBatch:
             return total[0], results, rows, None
         return total[0], results, rows, (out[:int(total["out_bytes"][0])] if out is not None else np.zeros(0, dtype=np.uint8))
 
+    # -- snapshots and checkpoints: ragged CRC batches, images, validation (include/ra_gpu_wal.h) --
+    def crc32_spans_device(self, spans: np.ndarray, d_data: int, data_bytes: int, d_crcs: int, stream: int = 0):
+        """d_crcs[i] = erlang:crc32(init_i, span i) for `spans` (abi.CRC_SPAN_DTYPE, a host array) over a device
+        buffer: accept_chunk/2 of every transfer in flight (src/ra_log_snapshot.erl:104-108); enqueues and returns."""
+        spans = np.ascontiguousarray(spans, dtype=abi.CRC_SPAN_DTYPE)
+        self._check(self._L.rgb_crc32_spans_device(self._h, spans.ctypes.data if len(spans) else None, len(spans),
+                                                   d_data or None, data_bytes, d_crcs or None, stream or None),
+                    "rgb_crc32_spans_device")
+
+    def crc32_spans(self, spans: np.ndarray, data) -> np.ndarray:
+        """Host-buffer form of crc32_spans_device: zlib.crc32(span, init) per span."""
+        spans = np.ascontiguousarray(spans, dtype=abi.CRC_SPAN_DTYPE)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        out = np.zeros(len(spans), dtype=np.uint32)
+        self._check(self._L.rgb_crc32_spans(self._h, spans.ctypes.data if len(spans) else None, len(spans),
+                                            data.ctypes.data if len(data) else None, len(data),
+                                            out.ctypes.data if len(spans) else None), "rgb_crc32_spans")
+        return out
+
+    def snapshot_build_device(self, items: np.ndarray, d_data: int, data_bytes: int, d_out: int, out_bytes: int,
+                              d_crcs: int = 0, stream: int = 0):
+        """The snapshot.dat / indexes image of every item (abi.SNAP_ITEM_DTYPE, a host array, out_offset filled) into
+        d_out (src/ra_log_snapshot.erl:49-68, src/ra_snapshot.erl:1017-1026); enqueues and returns."""
+        items = np.ascontiguousarray(items, dtype=abi.SNAP_ITEM_DTYPE)
+        self._check(self._L.rgb_snapshot_build_device(self._h, items.ctypes.data if len(items) else None, len(items),
+                                                      d_data or None, data_bytes, d_out or None, out_bytes,
+                                                      d_crcs or None, stream or None), "rgb_snapshot_build_device")
+
+    def snapshot_build(self, items: np.ndarray, data, out: np.ndarray | None = None):
+        """Host-buffer form: (image bytes, the Crc of every image).  Without `out` the items are laid out back to
+        back from 0 (their out_offset is overwritten in a copy); with `out` they go where their out_offset says."""
+        items = np.ascontiguousarray(items, dtype=abi.SNAP_ITEM_DTYPE)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if out is None:
+            items, size = snapshot_layout(items)
+            out = np.zeros(size, dtype=np.uint8)
+        crcs = np.zeros(len(items), dtype=np.uint32)
+        self._check(self._L.rgb_snapshot_build(self._h, items.ctypes.data if len(items) else None, len(items),
+                                               data.ctypes.data if len(data) else None, len(data),
+                                               out.ctypes.data if len(out) else None, len(out),
+                                               crcs.ctypes.data if len(items) else None), "rgb_snapshot_build")
+        return out, crcs
+
+    def snapshot_validate_device(self, files: np.ndarray, d_files: int, files_bytes: int, d_infos: int, stream: int = 0):
+        """One abi.SNAP_INFO_DTYPE row per file of `files` (abi.SNAP_FILE_DTYPE, a host array) into d_infos:
+        recover/1, validate/1 and read_meta/1 (src/ra_log_snapshot.erl:176-266); enqueues and returns."""
+        files = np.ascontiguousarray(files, dtype=abi.SNAP_FILE_DTYPE)
+        self._check(self._L.rgb_snapshot_validate_device(self._h, files.ctypes.data if len(files) else None, len(files),
+                                                         d_files or None, files_bytes, d_infos or None, stream or None),
+                    "rgb_snapshot_validate_device")
+
+    def snapshot_validate(self, files: np.ndarray, file_bytes) -> np.ndarray:
+        """Host-buffer form of snapshot_validate_device: the info rows."""
+        files = np.ascontiguousarray(files, dtype=abi.SNAP_FILE_DTYPE)
+        file_bytes = np.ascontiguousarray(file_bytes, dtype=np.uint8)
+        infos = np.zeros(len(files), dtype=abi.SNAP_INFO_DTYPE)
+        self._check(self._L.rgb_snapshot_validate(self._h, files.ctypes.data if len(files) else None, len(files),
+                                                  file_bytes.ctypes.data if len(file_bytes) else None, len(file_bytes),
+                                                  infos.ctypes.data if len(files) else None), "rgb_snapshot_validate")
+        return infos
+
     # -- observability -----------------------------------------------------------------
     def snapshot(self) -> np.ndarray:
         rows = np.zeros(self.n_groups, dtype=abi.LEADERBOARD_DTYPE)
@@ -950,6 +1021,13 @@ def segment_layout(entries: np.ndarray, max_count: int = 4096):
     size = lib().rgb_segment_layout(entries.ctypes.data if len(entries) else None, len(entries), max_count,
                                     offs.ctypes.data if len(entries) else None)
     return offs, int(size)
+
+
+def snapshot_layout(items: np.ndarray, base: int = 0):
+    """(a copy of `items` with out_offset filled back to back from `base`, the offset behind the last image)"""
+    items = np.ascontiguousarray(items, dtype=abi.SNAP_ITEM_DTYPE).copy()
+    end = lib().rgb_snapshot_layout(items.ctypes.data if len(items) else None, len(items), base)
+    return items, int(end)
 
 
 def _compact_args(sources, live):
