@@ -7,8 +7,10 @@ device-resident paths -- only run on the GPU.)"""
 import numpy as np
 import pytest
 
+import fuzz
 import test_gpu_parity as G
 import vector_runner as VR
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 
 
@@ -24,6 +26,30 @@ def test_all_reference_vectors_through_the_c_abi(emulated_engine):
 def test_random_ticks_through_the_c_abi(emulated_engine, oracle_lib, n_members, seed, groups):
     """(5, 107, 1300) carries >= 4096 messages per round: rgb_submit takes the class-dispatch kernel."""
     G.test_hip_equals_oracle_on_random_ticks(emulated_engine, oracle_lib, n_members, seed, groups)
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_random_ticks_under_permuted_schedules(emulated_engine, oracle_lib, sched):
+    """One random-ticks case per group size through rgb_submit's per-round launches with the emulation's workgroups and
+    lanes reversed and permuted (tests/emu_schedule.py): the staging, the class dispatch, the results kernels and the
+    checksum must not depend on which workgroup or lane runs first."""
+    with schedule(emulated_engine, sched):
+        for n_members in range(1, 9):
+            rng = np.random.default_rng(110 + n_members)
+            groups = 80
+            st = fuzz.random_states(rng, groups, n_members, max_runs=6)
+            cpu = oracle_lib.Oracle(groups, n_members)
+            cpu.set_state(0, st)
+            with emulated_engine.RaGpuBatch(groups, n_members, ring_capacity=4096, ring_slots=2, max_runs=16) as gpu:
+                gpu.set_state(0, st)
+                for tick in range(4):
+                    msgs = fuzz.random_msgs(rng, cpu.get_state(), n_members)
+                    do, ro = cpu.step(msgs)
+                    dg, rg = gpu.step(msgs)
+                    G.assert_same(f"N={n_members} tick {tick}", dg, rg, gpu.get_state(), do, ro, cpu.get_state())
+                want = emulated_engine.combine_checksums(oracle_lib.server_checksums(cpu.get_state()))
+                assert gpu.state_checksum() == want, f"N={n_members}: checksum"
+            cpu.close()
 
 
 def test_sub_ticks_ring_and_overflow(emulated_engine, oracle_lib):

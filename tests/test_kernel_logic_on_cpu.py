@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from ra_amd import abi, engine
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 import fuzz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -245,6 +246,48 @@ class KernelEmu(Emu):
 @pytest.mark.parametrize("mode", ["classes", "generic"])
 @pytest.mark.parametrize("n_members,seed", [(3, 321), (5, 322), (8, 323)])
 def test_whole_kernels_equal_checker_on_random_ticks(emu_lib, oracle_lib, n_members, seed, mode):
+    check_whole_kernels(emu_lib, oracle_lib, n_members, seed, mode)
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_whole_kernels_under_permuted_schedules(emu_lib, oracle_lib, sched):
+    """One random-ticks case per group size through the per-tick launches (class dispatch, the generic kernel for N = 4,
+    pack / unpack, checksum, leaderboard) with workgroups and lanes reversed and permuted (tests/emu_schedule.py): a
+    tick holds at most one message per server, so nothing in it may depend on which workgroup or lane runs first."""
+    with schedule(emu_lib, sched):
+        for n_members in range(1, 9):
+            try:
+                check_whole_kernels(emu_lib, oracle_lib, n_members, 330 + n_members, "generic" if n_members == 4 else "classes")
+            except AssertionError as e:
+                raise AssertionError(f"N={n_members}: {e}") from e
+
+
+def test_schedule_setting_and_the_wavefronts_lane_mode(emu_lib, oracle_lib):
+    """emu_set_schedule itself: it returns the previous modes, refuses a mode that does not exist without changing
+    anything, and the helper refuses to set one schedule over another; then one whole-kernels case with the 64-lane
+    groups permuted and the lanes inside ascending (the lane mode kept for kernels that exchange data inside a wavefront
+    without a workgroup barrier: none of the schedule tests needs it, so it runs here)."""
+    import emu_schedule as ES
+    fn = ES.setter(emu_lib)
+    try:
+        assert fn(ES.PERMUTED, ES.WAVEFRONTS, 7) == 0                      # from the default: ascending / ascending
+        assert fn(ES.DESCENDING, ES.PERMUTED, 8) == ES.PERMUTED | ES.WAVEFRONTS << 8
+        for bad in ((3, 0), (-1, 0), (0, 4), (0, -1)):                      # (blocks have no wavefronts mode)
+            assert fn(bad[0], bad[1], 9) == -1
+        assert fn(ES.ASCENDING, ES.ASCENDING, 0) == ES.DESCENDING | ES.PERMUTED << 8
+        fn(ES.DESCENDING, ES.ASCENDING, 0)
+        with pytest.raises(AssertionError, match="not ascending"):
+            with ES.schedule(emu_lib, "reverse"):
+                pass
+        assert fn(ES.ASCENDING, ES.ASCENDING, 0) == 0                      # ... and the helper put ascending back
+    finally:
+        fn(ES.ASCENDING, ES.ASCENDING, 0)
+    with schedule(emu_lib, "shuffle-1", wavefronts=True) as tag:
+        assert "lanes wavefronts permuted" in tag and "0x5eed0001" in tag
+        check_whole_kernels(emu_lib, oracle_lib, 5, 335, "classes")
+
+
+def check_whole_kernels(emu_lib, oracle_lib, n_members, seed, mode):
     rng = np.random.default_rng(seed)
     G = 120
     st = fuzz.random_states(rng, G, n_members, max_runs=6)

@@ -21,6 +21,7 @@ import zlib
 import numpy as np
 import pytest
 
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi, engine as product_engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -481,6 +482,18 @@ def test_emu_refusals(emu):
 
 def test_emu_round_trip(emu):
     check_round_trip(emu)
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_emu_under_permuted_schedules(emu, sched):
+    """The emulation's own order is workgroups 0, 1, 2, ... and lanes 0 .. 255.  The build cases (every lane-group
+    width), the stream CRC (its partial values are joined by a later launch) and the round trip with workgroups and lanes
+    reversed and permuted (tests/emu_schedule.py); the referee stays zlib and struct.pack."""
+    with schedule(emu.engine, sched):
+        for small in (0, 1, 2):
+            check_build_cases(emu, small)
+        check_stream(emu)
+        check_round_trip(emu)
 
 
 def test_segment_scan_under_sanitizers(tmp_path):

@@ -22,6 +22,7 @@ import zlib
 import numpy as np
 import pytest
 
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 from test_segment import Emu, Gpu, emu, gpu, first_diff, python_segment          # noqa: F401  (fixtures)
 
@@ -677,6 +678,52 @@ def check_status_precedence(be, width, flags):
     assert got == (CRC, 0, k) if flags & VERIFY else isinstance(got, bytes)
 
 
+SPREAD_RECORDS = 600            # three steps of the resolve pass; 19 to 150 workgroups of the copy, by the lane-group width
+SPREAD_PLACES = (330, 200, 40)  # 40 and 200: one step of the resolve pass, two wavefronts; 40 and 330: 290 places apart
+
+
+def check_spread_faults(be, width, flags):
+    """The SAME fault at three places of one source's copy order, far apart: the answer is the first in copy order, and
+    the kernels find it as a minimum over atomics (s_miss_k, s_trunc_k, hdr->crc_fail, s_first_zero) that reach their
+    word in whatever order lanes and workgroups run.  Places 40 and 200 meet in one step of the resolve pass, on
+    different wavefronts; 40 and 330 are 290 places apart, in different workgroups of the copy.  Referee: ref_compact."""
+    n, first = SPREAD_RECORDS, min(SPREAD_PLACES)
+    verify = bool(flags & VERIFY)
+
+    def records(skip=()):
+        return [R(i, 2, bytes([i % 251]) * 20) for i in range(1, n + 1 + len(skip)) if i - 1 not in skip]
+
+    def run(files, lives, expect, what):
+        files = pad_to_width(files, sum(len(_expand(l)) for l in lives), width)
+        got = check_group(be, files, lives, flags=flags, host_form=False, what=what)
+        assert (got == expect) if expect is not None else isinstance(got, bytes), f"{what}: the referee says {got}, want {expect}"
+
+    recs = records()
+    for p in SPREAD_PLACES:
+        recs[p]["crc"] = 0x1234567
+    run([make_source(recs)], [[(1, n)]], (CRC, 0, first + 1) if verify else None, "three Crc mismatches")
+    recs = records()
+    for p in SPREAD_PLACES:
+        recs[p]["off"] = 1 << 40
+    run([make_source(recs)], [[(1, n)]], (TRUNCATED, 0, first + 1), "three truncated records")
+    # three live indexes that the file does not have: every selected record behind the first of them is off its rank
+    run([make_source(records(skip=SPREAD_PLACES))], [[(1, n + 3)]], (MISSING, 0, first + 1), "three missing indexes")
+    # one of each, the later place the higher-ranking kind
+    recs = records(skip=(330,))
+    recs[200]["off"] = 1 << 40
+    recs[40]["crc"] = 0x1234567
+    run([make_source(recs)], [[(1, n + 1)]], (TRUNCATED, 0, 201), "Crc at 40, TRUNCATED at 200, MISSING at 330")
+    # the fault of the LOWER-numbered source lies later in its copy order than the fault of the next source
+    a, b = records(), [R(1000 + i, 3, bytes([i]) * 20) for i in range(60)]
+    a[330]["crc"] = b[5]["crc"] = 0x1234567
+    run([make_source(a), make_source(b)], [[(1, n)], [(1000, 1059)]], (CRC, 0, 331) if verify else None,
+        "a mismatch at place 330 of source 0 and at place 5 of source 1")
+    # the walk ends at the first all-zero record: 40 records and 300 unused ones, 216 of them in the first step
+    short = make_source(records()[:first], max_count=first + 300)
+    check_info(be, [short], [[(1, first)]], "300 all-zero records behind 40")
+    run([short], [[(1, first)]], None, "300 all-zero records behind 40")
+
+
 def malformed_descriptors():
     """(name, sources, live pairs, files_bytes, flags) -- each is RGB_E_INVAL"""
     def src(*rows):
@@ -808,6 +855,29 @@ def test_emu_status_precedence(emu, width, flags):
     check_status_precedence(emu, width, flags)
 
 
+@pytest.mark.parametrize("flags", [0, VERIFY], ids=["plain", "verify"])
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_emu_spread_faults(emu, width, flags):
+    check_spread_faults(emu, width, flags)
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_emu_under_permuted_schedules(emu, sched):
+    """The emulation's own order is workgroups 0, 1, 2, ... and lanes 0 .. 255, so every "first in order" that the
+    kernels take as a minimum over atomics also arrives first.  The checks whose answers are such minima, sums and bit
+    sets once more with workgroups and lanes reversed and permuted (tests/emu_schedule.py); the referee stays
+    ref_compact / ref_info."""
+    with schedule(emu.engine, sched):
+        for width in (8, 16, 64):
+            for flags in (0, VERIFY):
+                check_status_precedence(emu, width, flags)
+                check_spread_faults(emu, width, flags)
+        check_effective_scan(emu, 257)
+        check_effective_scan(emu, 1000)
+        check_same_index_in_two_sources(emu)
+        check_statuses(emu)
+
+
 def test_emu_argument_errors(emu):
     check_argument_errors(emu)
 
@@ -922,6 +992,13 @@ def test_gpu_statuses(gpu):
 @pytest.mark.parametrize("width", [8, 16, 64])
 def test_gpu_status_precedence(gpu, width, flags):
     check_status_precedence(gpu, width, flags)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [0, VERIFY], ids=["plain", "verify"])
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_gpu_spread_faults(gpu, width, flags):
+    check_spread_faults(gpu, width, flags)
 
 
 @pytest.mark.gpu

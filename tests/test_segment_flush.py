@@ -23,6 +23,7 @@ import zlib
 import numpy as np
 import pytest
 
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 from test_segment import Emu, Gpu, emu, gpu, first_diff, force_group, python_segment          # noqa: F401  (fixtures)
 
@@ -572,6 +573,31 @@ def check_statuses_and_errors(be):
         assert int(res_h["status"]) == OK and len(pieces_h) == 0 and len(out_h) == 0
 
 
+def check_spread_bad_entries(be):
+    """ENTRY names the first entry, in entry order, whose payload lies outside d_data: a 64-bit minimum over atomics
+    (s_bad of the plan pass, then over the workgroups' totals in the place pass) that arrive in whatever order lanes and
+    workgroups run.  Three bad entries far apart -- two in one workgroup of the plan on different wavefronts, the third
+    more than 256 entries on in another workgroup -- at both ends of the sub-group widths; the same calls without the
+    damage go against the referee."""
+    rng = np.random.default_rng(775)
+    for n_writers, per, bad_at in ((12, 30, (300, 50, 20)),        # a wavefront per writer: 4 writers, 3 workgroups
+                                   (100, 4, (330, 200, 40))):      # 8 lanes per writer: 32 writers, 4 workgroups
+        specs = [mk_writer(rng, [int(x) for x in rng.integers(0, 20, size=per)], omax=5, ocount=w % 3, oidx=100 * w + 1)
+                 for w in range(n_writers)]
+        what = f"{n_writers} writers of {per} entries"
+        run_case(be, rng, specs, 4, 100, host_form=False, what=what)
+        writers, entries, data, _ = build_call(rng, specs)
+        assert len(entries) == n_writers * per and max(bad_at) - min(bad_at) > 256
+        for field, value in (("data_len", len(data) + 1), ("data_offset", (1 << 64) - 4)):
+            bad = entries.copy()
+            for e in bad_at:
+                bad[field][e] = value
+            res, rows, region = device_flush(be, writers, bad, data, 4, 100)
+            got = (int(res["status"]), int(res["entry"]), int(res["writer"]))
+            assert got == (ENTRY, min(bad_at), min(bad_at) // per), f"{what}, {field} of {bad_at}: {got}"
+            assert np.all(rows == 0xEE) and np.all(region == 0xEE), f"{what}: ENTRY, but something was written"
+
+
 def random_specs(rng, trial):
     n_w = int(rng.integers(0, 6))
     long_one = trial % 7 == 0
@@ -716,6 +742,23 @@ def test_emu_back_to_back_calls(emu):
     check_back_to_back_calls(emu)
 
 
+def test_emu_spread_bad_entries(emu):
+    check_spread_bad_entries(emu)
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_emu_under_permuted_schedules(emu, sched):
+    """The emulation's own order is workgroups 0, 1, 2, ... and lanes 0 .. 255, so the first bad entry also arrives
+    first at the minimum that finds it, and every workgroup of the place pass runs behind its predecessors.  The checks
+    that span several workgroups once more with workgroups and lanes reversed and permuted (tests/emu_schedule.py);
+    the referee stays ref_flush."""
+    with schedule(emu.engine, sched):
+        check_chunk_edges(emu)
+        check_statuses_and_errors(emu)
+        check_spread_bad_entries(emu)
+        check_random_sweep(emu, 100, 40)
+
+
 def test_flush_descriptors_under_sanitizers(tmp_path):
     """rgb_segment_flush_bound -- the host-side validation of every flush call, in the host-only unit
     rgb_segment_host.cpp -- compiled with AddressSanitizer + UBSan into a stand-alone program and run over the malformed
@@ -818,6 +861,11 @@ def test_gpu_random_sweep(gpu):
 @pytest.mark.gpu
 def test_gpu_back_to_back_calls(gpu):
     check_back_to_back_calls(gpu)
+
+
+@pytest.mark.gpu
+def test_gpu_spread_bad_entries(gpu):
+    check_spread_bad_entries(gpu)
 
 
 @pytest.mark.gpu

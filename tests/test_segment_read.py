@@ -25,6 +25,7 @@ import zlib
 import numpy as np
 import pytest
 
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 from test_segment import Emu, Gpu, emu, gpu, first_diff, python_segment          # noqa: F401  (fixtures)
 from test_segment_compact import R, make_source, pad_to_width, ref_parse, scan_patterns, source_of
@@ -395,6 +396,48 @@ def check_failures(be, width):
             assert [k for s, k in enumerate(ks) if s != place] == [k for s, k in enumerate([OK, OK, OK, MISSING, OK]) if s != place]
 
 
+SPREAD_REQUESTS = 600           # three steps of the resolve pass; 19 to 150 workgroups of the copy, by the lane-group width
+SPREAD_POSITIONS = (330, 200, 40)   # 40 and 200: one step of the resolve pass, two wavefronts; 40 and 330: 290 apart
+
+
+def check_spread_failures(be, width):
+    """The SAME failure at three positions of one source's requests, far apart, the requests in DESCENDING index order
+    (the later position asks for the lower-numbered record): the answer is the first position, which the kernels find
+    as a minimum over atomics (s_miss_k, s_trunc_k of the resolve pass, crc_k[source] of the copy) that arrive in
+    whatever order lanes and workgroups run.  Positions 40 and 200 meet in one step of the resolve pass, on different
+    wavefronts; 40 and 330 lie in different workgroups of the copy.  Referee: ref_read, byte for byte."""
+    n, first = SPREAD_REQUESTS, min(SPREAD_POSITIONS)
+    rng = np.random.default_rng(745 + width)
+    pay = [rng.integers(0, 256, size=20, dtype=np.uint8).tobytes() for _ in range(n)]
+    ask = list(range(1000 + n - 1, 999, -1))                # position k asks for record 1000 + n - 1 - k
+    hit = [ask[k] for k in SPREAD_POSITIONS]
+
+    def src(how):
+        recs = []
+        for j, p in enumerate(pay):
+            if 1000 + j not in hit or how is None:
+                recs.append(R(1000 + j, 1, p))
+            elif how == "crc":
+                recs.append(R(1000 + j, 1, damaged(p), crc=zlib.crc32(p)))
+            else:
+                recs.append(R(1000 + j, 1, p, off=1 << 40))
+        return make_source(recs)
+
+    gone = list(ask)
+    for k in SPREAD_POSITIONS:
+        gone[k] = 99                                        # an index the file does not have
+    mixed = list(ask)
+    mixed[330] = 99                                         # MISSING at 330, TRUNCATED at 200 and 40 (of the "trunc" file)
+    files = [src("crc"), src("trunc"), src(None), src("trunc"), src(None)]
+    reqs = [ask, ask, gone, mixed, ask]
+    files = pad_to_width(files, sum(len(r) for r in reqs), width)
+    slices, req = slices_of(reqs)
+    plain = [(OK, n, 0), (TRUNCATED, first, ask[first]), (MISSING, first, 99), (TRUNCATED, first, ask[first]), (OK, n, 0)]
+    for flags in (0, VERIFY):
+        want = check_read(be, files, slices, req, flags, host_form=False, what=f"spread failures, width {width}, flags {flags}")
+        assert want["statuses"] == ([(CRC, first, ask[first])] if flags else plain[:1]) + plain[1:]
+
+
 def check_sizing_and_modes(be):
     rng = np.random.default_rng(750)
     f0, f1 = source_of(rng, list(range(1, 40))), source_of(rng, list(range(50, 90)))
@@ -653,6 +696,25 @@ def test_emu_failures(emu, width):
     check_failures(emu, width)
 
 
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_emu_spread_failures(emu, width):
+    check_spread_failures(emu, width)
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_emu_under_permuted_schedules(emu, sched):
+    """The emulation's own order is workgroups 0, 1, 2, ... and lanes 0 .. 255, so "the first failing position", which
+    the kernels take as a minimum over atomics, also arrives first.  The checks that reach those atomics once more with
+    workgroups and lanes reversed and permuted (tests/emu_schedule.py); the referee stays ref_read."""
+    with schedule(emu.engine, sched):
+        for width in (8, 16, 64):
+            check_failures(emu, width)
+            check_spread_failures(emu, width)
+        check_many_sources(emu)
+        check_composition(emu)
+        check_fuzz(emu, 7900)
+
+
 def test_emu_sizing_and_modes(emu):
     check_sizing_and_modes(emu)
 
@@ -787,6 +849,12 @@ def test_gpu_payloads(gpu, width, flags):
 @pytest.mark.parametrize("width", [8, 16, 64])
 def test_gpu_failures(gpu, width):
     check_failures(gpu, width)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [8, 16, 64])
+def test_gpu_spread_failures(gpu, width):
+    check_spread_failures(gpu, width)
 
 
 @pytest.mark.gpu

@@ -20,6 +20,7 @@ import zlib
 import numpy as np
 import pytest
 
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 from test_segment import (E_INVAL, ROOT, STREAM_BLOCK, emu, first_diff, gf2_mulmod, gf2_xpow8, gpu,  # noqa: F401
                           raw_crc)
@@ -483,6 +484,24 @@ CHECKS = [check_spans_every_length_and_phase, check_spans_boundaries, check_span
 @pytest.mark.parametrize("check", CHECKS, ids=[c.__name__[6:] for c in CHECKS])
 def test_emu(emu, check):
     check(emu)
+
+
+SCHEDULE_CHECKS = [check_span_batches, check_images_blocks, check_validate_independent, check_spans_second_combine_round]
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_emu_under_permuted_schedules(emu, sched):
+    """Every pass of the snapshot kernels is its own launch "so that no workgroup ever waits for another", and on the
+    emulation's own order (workgroups 0, 1, 2, ..., lanes 0 .. 255) a workgroup that read what a lower-numbered one
+    wrote in the same launch would still be right.  The checks that span many workgroups -- batches of 257 and 513
+    items, pieces of several blocks, 300 files, the second join round -- with workgroups and lanes reversed and permuted
+    (tests/emu_schedule.py); the referee stays zlib."""
+    with schedule(emu.engine, sched):
+        for check in SCHEDULE_CHECKS:
+            try:
+                check(emu)
+            except AssertionError as e:
+                raise AssertionError(f"{check.__name__}: {e}") from e
 
 
 def test_abi_mirror():

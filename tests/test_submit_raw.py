@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import fuzz
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -517,6 +518,111 @@ def test_trains_fallback_sees_an_invalid_record_behind_65536_messages_of_one_ser
 @pytest.mark.gpu
 def test_gpu_trains_fallback(gpu_engine, oracle_lib):
     check_trains_fallback(gpu_engine, oracle_lib, G=1500)
+
+
+# ------------------------------------------------------------------------------------------ 4b. spread batches
+
+SPREAD_N, SPREAD_ROUNDS = 5, 8
+SPREAD_GROUPS = 52              # the fewest groups of five with groups x n_members >= 256: a tick spans two workgroups
+SPREAD_LAYOUTS = ("round-major", "server-major", "round-major reversed", "server-major reversed")
+
+
+def spread_batch(rng, state, n_members, rounds, layout):
+    """`rounds` ticks with a message for EVERY server (frac = 1.0), laid out on purpose instead of shuffled:
+    round-major   the ticks one behind the other, each in server order: a server's messages lie exactly len(state)
+                  records apart, each in another workgroup of 256 records
+    server-major  a stable sort of that by server: a server's messages are adjacent, inside one wavefront
+    `... reversed`: the same records back to front."""
+    ticks = [fuzz.random_msgs(rng, state, n_members, frac=1.0) for _ in range(rounds)]
+    msgs = np.concatenate([t[np.argsort(t["server"], kind="stable")] for t in ticks])
+    assert len(msgs) == rounds * len(state)
+    if layout.startswith("server-major"):
+        msgs = msgs[np.argsort(msgs["server"], kind="stable")]
+    if layout.endswith("reversed"):
+        msgs = msgs[::-1].copy()
+    return msgs
+
+
+def check_spread_batches(engine, O, groups, n_members=SPREAD_N, rounds=SPREAD_ROUNDS, seed=71, tag=""):
+    """Every layout of SPREAD_LAYOUTS through rgb_submit (A), rgb_submit_raw (B) and begin / commit (C): decisions and
+    rpc records byte-equal between the three and equal to the sequential checker's, the states as check_differential
+    compares them."""
+    rng = np.random.default_rng(seed)
+    S = groups * n_members
+    assert S >= 256
+    st = fuzz.random_states(rng, groups, n_members, max_runs=6)
+    cpu = O.Oracle(groups, n_members, max_runs=16)
+    cpu.set_state(0, st)
+    n = rounds * S
+    ring_capacity = sum(n // (r + 1) for r in range(rounds))
+    mk = lambda: engine.RaGpuBatch(groups, n_members, ring_capacity=ring_capacity, ring_slots=2, max_runs=16)
+    with mk() as a, mk() as b, mk() as c:
+        for g in (a, b, c):
+            g.set_state(0, st)
+        assert b.raw_capacity(rounds) >= n
+        for k, layout in enumerate(SPREAD_LAYOUTS):
+            msgs = spread_batch(rng, cpu.get_state(), n_members, rounds, layout)
+            where = f"{tag}{layout}, {groups} groups of {n_members}, {len(msgs)} messages"
+            # the layout is what it says: a server's messages a tick apart, or adjacent
+            live = np.flatnonzero(msgs["server"] == msgs["server"][0])
+            assert len(live) == rounds, where
+            if layout.startswith("round-major"):
+                assert np.all(np.diff(live) == S) and len(set(live // 256)) == rounds, where
+            else:
+                assert np.all(np.diff(live) == 1), where
+            do, ro = cpu.step(msgs)
+            a.submit(msgs, tick=k)
+            da, ra, _ = a.collect()
+            b.submit_raw(msgs, tick=k, max_rounds=rounds)
+            db, rb, tb = b.collect()
+            fill_and_commit(c, msgs, k, rounds)
+            dc, rc, tc, slot = c.collect_view()
+            assert tb == k and tc == k, where
+            assert db.tobytes() == da.tobytes(), where + ": raw decisions differ from rgb_submit's"
+            assert rb.tobytes() == ra.tobytes(), where + ": raw rpc records differ from rgb_submit's"
+            assert dc.tobytes() == da.tobytes() and rc.tobytes() == ra.tobytes(), where + ": begin/commit + view"
+            c.release(slot)
+            assert db.tobytes() == do.tobytes(), where + ": decisions differ from the checker's"
+            assert fuzz.sort_rpcs(rb.copy()).tobytes() == fuzz.sort_rpcs(ro).tobytes(), where + ": rpcs vs checker"
+            want = cpu.get_state()
+            assert_state_equal(where + " (rgb_submit)", a.get_state(), want)
+            assert_state_equal(where + " (rgb_submit_raw)", b.get_state(), want)
+            assert_state_equal(where + " (begin/commit)", c.get_state(), want)
+    cpu.close()
+
+
+@pytest.mark.parametrize("sched", ("ascending",) + PERMUTED_SCHEDULES)
+def test_spread_batches(emulated_engine, oracle_lib, sched):
+    with schedule(emulated_engine, sched) as tag:
+        check_spread_batches(emulated_engine, oracle_lib, SPREAD_GROUPS, tag=tag + ": ")
+
+
+@pytest.mark.gpu
+def test_gpu_spread_batches(gpu_engine, oracle_lib):
+    check_spread_batches(gpu_engine, oracle_lib, SPREAD_GROUPS * 16)
+
+
+# ------------------------------------------------------------------------------------------ 4c. permuted schedules
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_raw_path_under_permuted_schedules(emulated_engine, oracle_lib, sched):
+    """The emulation runs workgroups and lanes in index order unless told otherwise, and then every atomic of
+    rgb_prepare.hip arrives in submission order: its sorting step has nothing to do.  The checks of this module once
+    more with the workgroups and the lanes reversed, and permuted (tests/emu_schedule.py); the referee stays the
+    sequential checker.  check_trains_fallback runs with 260 groups, the fewest whose batches stay above its own floor
+    of 4096 messages with some room (at the 1200 of test_trains_fallback_on_the_emulation it alone costs more than the
+    rest of this module): on such a context the raw calls run rgb_submit's host passes and launch no kernel of
+    rgb_prepare.hip; what the schedules reach there is the train launch of rgb_submit, on the emulation always the
+    persistent form (see test_train_on_the_block_emulation_under_permuted_schedules)."""
+    with schedule(emulated_engine, sched):
+        for n_members, rounds, groups, seed in DIFF_CASES:
+            try:
+                check_differential(emulated_engine, oracle_lib, n_members, rounds, groups, seed)
+            except AssertionError as e:
+                raise AssertionError(f"DIFF_CASES N={n_members} rounds={rounds} seed={seed}: {e}") from e
+        check_refusals(emulated_engine, oracle_lib)
+        check_ordering(emulated_engine, oracle_lib)
+        check_trains_fallback(emulated_engine, oracle_lib, G=260)
 
 
 # ------------------------------------------------------------------------------------------ 5. resources

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from emu_schedule import PERMUTED_SCHEDULES, schedule
 from ra_amd import abi
 from ra_amd import workload as W
 
@@ -199,6 +200,21 @@ def check_train_equals_per_tick_launches(engine, oracle_lib, G, N, T, seed, on_g
 @pytest.mark.parametrize("G,N,T,seed", [(192, 5, 20, 0x5EED0003), (96, 3, 12, 7), (64, 7, 10, 11), (72, 6, 8, 13), (80, 8, 8, 17)])
 def test_train_on_the_block_emulation(emulated_engine, oracle_lib, G, N, T, seed):
     check_train_equals_per_tick_launches(emulated_engine, oracle_lib, G, N, T, seed, False, chunks=(None, 3))
+
+
+@pytest.mark.parametrize("sched", PERMUTED_SCHEDULES)
+def test_train_on_the_block_emulation_under_permuted_schedules(emulated_engine, oracle_lib, sched):
+    """One case of test_train_on_the_block_emulation with workgroups and lanes reversed and permuted
+    (tests/emu_schedule.py).  Every train launch of the emulation is the PERSISTENT form, rgb_train_kernel: the
+    emulation reports one XCC (rgb_xcc_id() is 0 there), and rgb_train_setup takes the dealt form only after a
+    calibration launch that saw eight -- whether the plan was built by the host or on the device has no part in it.  The
+    persistent kernel never reads blockIdx (a workgroup takes its shard from an arrival counter and its rows from the
+    shard's ticket counter, and waits only for smaller tickets), so for it the block order changes nothing and the lane
+    order is what this test adds; the block order reaches the other kernels of the check (the per-tick launches, the
+    stamps, the plan kernel, pack / unpack).  rgb_train_dealt_kernel, which polls what lower-numbered workgroups
+    publish, is not run by any CPU test, under any schedule: its tests are the -m gpu ones."""
+    with schedule(emulated_engine, sched):
+        check_train_equals_per_tick_launches(emulated_engine, oracle_lib, 96, 3, 12, 7, False, chunks=(None, 3))
 
 
 @pytest.mark.parametrize("G,N,T,seed", [(160, 5, 12, 21), (64, 7, 8, 23)])

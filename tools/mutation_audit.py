@@ -11,6 +11,8 @@ Every entry of tools/mutation_audit.json is one small change of a product source
     what        one line for the report
     equivalent  (optional) why no test can notice: the mutant computes the same thing
     gpu_only    (optional) the -m gpu tests that notice it where no CPU test can; reported apart, never run here
+    open        (optional) why no test, on the CPU or on the GPU, is known to notice it although it is a real fault;
+                reported apart as OPEN, and stale once a test kills it
 
 Per mutant the tool copies the tree to a throw-away directory, applies the change there, builds the emulation library
 (the units of tests/conftest.py with its flags), runs the named modules with -m "not gpu" -- without the sanitizer
@@ -23,7 +25,7 @@ with the other objects.  The copy's tests get that library through one fixture a
 (a later definition of `emulated_kernels_so` that returns the path, and ra_amd.engine bound to the same library for the
 host-only entry points that tests call directly); the repository's conftest is not changed.
 
-Exit status 0: every mutant is killed, or explained (`equivalent`, at most a quarter of the list) or `gpu_only`.
+Exit status 0: every mutant is killed, or explained (`equivalent`, at most a quarter of the list), `gpu_only` or `open`.
 
 usage: python tools/mutation_audit.py [--tree DIR] [--only ID[,ID...]] [--jobs N] [--stop-at-first]
                                       [--subst OLD=NEW] [--json OUT]
@@ -204,7 +206,7 @@ def main():
             futs = [pool.submit(run_mutant, m, tree, base, deps, a.stop_at_first, a.timeout) for m in mutants]
             for m, f in zip(mutants, futs):
                 r = f.result()
-                r["equivalent"], r["gpu_only"] = m.get("equivalent", ""), m.get("gpu_only", [])
+                r["equivalent"], r["gpu_only"], r["open"] = m.get("equivalent", ""), m.get("gpu_only", []), m.get("open", "")
                 results.append(r)
                 line = "%3d  %-9s %s" % (r["id"], r["outcome"], r["what"])
                 if r["outcome"] == "killed":
@@ -214,6 +216,8 @@ def main():
                     line += "\n       equivalent: " + r["equivalent"]
                 elif r["outcome"] == "survived" and r["gpu_only"]:
                     line += "\n       killed on the GPU only: " + " ".join(r["gpu_only"])
+                elif r["outcome"] == "survived" and r["open"]:
+                    line += "\n       OPEN: " + r["open"]
                 elif r["note"]:
                     line += "\n       " + r["note"]
                 print(line, flush=True)
@@ -221,14 +225,15 @@ def main():
         json.dump(results, open(a.json, "w"), indent=1)
     killed = [r for r in results if r["outcome"] == "killed"]
     surv = [r for r in results if r["outcome"] == "survived"]
-    unexplained = [r["id"] for r in surv if not r["equivalent"] and not r["gpu_only"]]
-    stale = [r["id"] for r in killed if r["equivalent"]]
+    unexplained = [r["id"] for r in surv if not r["equivalent"] and not r["gpu_only"] and not r["open"]]
+    stale = [r["id"] for r in killed if r["equivalent"] or r["open"]]
     broken = [r["id"] for r in results if r["outcome"] in ("refused", "error")]
-    print("%d killed, %d survived (%d equivalent, %d killed on the GPU only, %d unexplained), %d refused or in error"
+    print("%d killed, %d survived (%d equivalent, %d killed on the GPU only, %d open, %d unexplained), %d refused or in error"
           % (len(killed), len(surv), sum(1 for r in surv if r["equivalent"]),
-             sum(1 for r in surv if r["gpu_only"] and not r["equivalent"]), len(unexplained), len(broken)))
+             sum(1 for r in surv if r["gpu_only"] and not r["equivalent"]),
+             sum(1 for r in surv if r["open"] and not r["equivalent"] and not r["gpu_only"]), len(unexplained), len(broken)))
     if stale:
-        print("closed as equivalent, but killed:", stale)
+        print("closed as equivalent or open, but killed:", stale)
     if unexplained:
         print("unexplained survivors:", unexplained)
     return 1 if unexplained or broken or stale else 0
