@@ -20,6 +20,7 @@
 -export([wal_batch_checksums/2, wal_frame/4, wal_recover_check/2, wal_frame_batch/3, wal_recover/2]).
 -export([crc32s/3, crc32_stream/3, segment_build/5, segment_image/4]).
 -export([segment_info/4, segment_compact/6, segment_compact_group/4]).
+-export([segment_compact_plan/7, segment_compact_groups/7, major_compaction_batch/4]).
 -export([segment_flush/7, segment_flush_batch/5]).
 -export([segment_read/5, segment_read_plan/3, segment_term_query_batch/2]).
 -export([crc32_spans/3, snapshot_build/3, snapshot_validate/3, snapshot_images/2, snapshot_recover_batch/2, accept_chunks/2]).
@@ -182,6 +183,85 @@ segment_compact_group(Ctx, Group, MaxSize, Verify) ->
                     end, {<<>>, [], <<>>, 0, 0}, Group),
     Flags = case Verify of true -> 1; false -> 0 end,
     segment_compact(Ctx, SourcesBin, iolist_to_binary(Files), LiveBin, MaxSize, Flags).
+
+%% major compaction for many members in one call: the plan, then the copy of every group (the .compaction_group
+%% marker of src/ra_log_segments.erl:783-786 is written between the two).  MembersBin = one 16-byte record per member:
+%% segref_first:32, segref_n:32 (its files inside SegrefsBin, newest first as compactable_segrefs/2 gives them),
+%% live_first:32, live_n:32 (its live pairs inside LiveBin).  SegrefsBin = one 32-byte record per file: offset:64,
+%% n_bytes:64 (the file inside FilesBin), range_first:64, range_last:64.  RowsBin = one 32-byte record per file:
+%% num_live:64, live_first:32, live_n:32 (its selection inside LiveOutBin), flags:32 (1 = unreferenced: the Delete list
+%% of both compaction kinds), group:32 (its group in GroupsBin, 16#FFFFFFFF = none), status:32 (1 = the member's
+%% take_group/3 would have raised badarith), 0:32.  GroupsBin = one 24-byte record per group: src_first:32, src_n:32,
+%% out_offset:64, out_bytes:64; the sources of the copy are the groups' files in GroupsBin order, oldest first.
+%% ResultsBin = one 32-byte record per group: status:32, n_entries:32, file_bytes:64, index:64, source:32, 0:32.
+%% A file with live indexes whose header is damaged makes segment_compact_plan answer {error, invalid} for the whole
+%% call (info/2 would crash that member's compaction); segment_compact_groups fails only that file's group.
+segment_compact_plan(_Ctx, _MembersBin, _SegrefsBin, _FilesBin, _LiveBin, _MaxCount, _MaxSize) ->
+    erlang:nif_error(not_loaded).
+segment_compact_groups(_Ctx, _GroupsBin, _SourcesBin, _FilesBin, _LiveBin, _MaxSize, _Flags) ->
+    erlang:nif_error(not_loaded).
+
+%% Members = [{[{FileBin, Range}], LiveSeq}]: per member its compactable files newest first with their segref ranges
+%% and its live indexes; Conf = #{max_count := _, max_size := _} (the compaction conf, also the segments' max_size).
+%% -> [{Unreferenced, [{GroupFileOrdinals, {ok, SegmentBin} | {error, _}}]}] per member: the ordinals (from 0) of the
+%% files without live indexes, and per group the ordinals of its files oldest first (the head is the group leader) with
+%% the new segment or what segment_compact_group/4 would have failed with.  A member whose grouping would have
+%% raised badarith has no groups.  Markers, renames, symlinks, deletes and sync_dir stay in ra_log_segments.
+major_compaction_batch(Ctx, Members, #{max_count := MaxCount, max_size := MaxSize}, Verify) ->
+    {MembersBin, SegrefsBin, Files, LiveBin, _, _, _} =
+        lists:foldl(
+          fun({FileRanges, LiveSeq}, {M, S, F, L, RefOff, FileOff, LiveOff}) ->
+                  Ranges = seq_ranges(LiveSeq),
+                  {S1, F1, FileOff1} =
+                      lists:foldl(fun({FileBin, {First, Last}}, {S0, F0, Off}) ->
+                                          Len = byte_size(FileBin),
+                                          {<<S0/binary, Off:64/little, Len:64/little, First:64/little, Last:64/little>>,
+                                           [F0, FileBin], Off + Len}
+                                  end, {S, F, FileOff}, FileRanges),
+                  NRefs = length(FileRanges),
+                  NLive = length(Ranges),
+                  {<<M/binary, RefOff:32/little, NRefs:32/little, LiveOff:32/little, NLive:32/little>>, S1, F1,
+                   << L/binary, << <<Lo:64/little, Hi:64/little>> || {Lo, Hi} <- Ranges >>/binary >>,
+                   RefOff + NRefs, FileOff1, LiveOff + NLive}
+          end, {<<>>, <<>>, [], <<>>, 0, 0, 0}, Members),
+    FilesBin = iolist_to_binary(Files),
+    {ok, RowsBin, GroupsBin, LiveOutBin} =
+        segment_compact_plan(Ctx, MembersBin, SegrefsBin, FilesBin, LiveBin, MaxCount, MaxSize),
+    Rows = [{LiveFirst, LiveN, Flags, Group}
+            || <<_NumLive:64/little, LiveFirst:32/little, LiveN:32/little, Flags:32/little, Group:32/little,
+                 _Status:32/little, _:32>> <= RowsBin],
+    Refs = [{Off, Len} || <<Off:64/little, Len:64/little, _:128>> <= SegrefsBin],
+    %% the sources of the copy: group by group, a group's files oldest first = its rows last to first
+    Tagged = lists:zip3(lists:seq(0, length(Rows) - 1), Rows, Refs),
+    %% (lists:sort/1 on the whole tuple: by group, then by -K, i.e. the member's LAST segref first)
+    InGroups = lists:sort([{Group, -K, Off, Len, LiveFirst, LiveN}
+                           || {K, {LiveFirst, LiveN, _, Group}, {Off, Len}} <- Tagged, Group =/= 16#FFFFFFFF]),
+    SourcesBin = << <<Off:64/little, Len:64/little, LiveFirst:32/little, LiveN:32/little, 0:64>>
+                    || {_, _, Off, Len, LiveFirst, LiveN} <- InGroups >>,
+    Flags = case Verify of true -> 1; false -> 0 end,
+    {ok, ResultsBin, OutBin} =
+        segment_compact_groups(Ctx, GroupsBin, SourcesBin, FilesBin, LiveOutBin, MaxSize, Flags),
+    Groups = [{OutOff, OutLen} || <<_:64, OutOff:64/little, OutLen:64/little>> <= GroupsBin],
+    Results = [R || <<R:32/binary>> <= ResultsBin],
+    Answers = [compact_groups_answer(R, OutOff, OutBin) || {R, {OutOff, _}} <- lists:zip(Results, Groups)],
+    {PerMember, _} =
+        lists:mapfoldl(
+          fun({FileRanges, _}, RefOff) ->
+                  N = length(FileRanges),
+                  Mine = [{K - RefOff, Row} || {K, Row, _} <- Tagged, K >= RefOff, K < RefOff + N],
+                  Unref = [K || {K, {_, _, F, _}} <- Mine, F band 1 =:= 1],
+                  Gs = lists:usort([G || {_, {_, _, _, G}} <- Mine, G =/= 16#FFFFFFFF]),
+                  {{Unref, [{lists:reverse([K || {K, {_, _, _, G1}} <- Mine, G1 =:= G]), lists:nth(G + 1, Answers)}
+                            || G <- Gs]}, RefOff + N}
+          end, 0, Members),
+    PerMember.
+
+compact_groups_answer(<<0:32/little, _:32, FileBytes:64/little, _/binary>>, OutOff, OutBin) ->
+    {ok, binary:part(OutBin, OutOff, FileBytes)};
+compact_groups_answer(<<1:32/little, _:32, _:64, Idx:64/little, _/binary>>, _, _) -> {error, {copy_missing_key, Idx}};
+compact_groups_answer(<<2:32/little, _/binary>>, _, _) -> {error, full};
+compact_groups_answer(<<St:32/little, _:32, _:64, Idx:64/little, Source:32/little, _:32>>, _, _) ->
+    {error, {case St of 3 -> truncated; 4 -> space; 5 -> crc; 6 -> bad_source end, Source, Idx}}.
 
 %% mem-table flush (src/ra_log_segment_writer.erl:268-329, 425-500): the entries of every writer of a rolled-over WAL
 %% appended to the writers' segment files in one call.  WritersBin = one 48-byte record per writer, little endian:

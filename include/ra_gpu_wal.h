@@ -243,8 +243,8 @@ int rgb_segment_validate(rgb_ctx *ctx, const void *bytes, uint64_t n_bytes, cons
  * indexes), so nothing is ever sorted.
  *
  * Choosing which live indexes belong to which source (ra_seq:in_range/2 and the progressive ra_seq:limit/2 of
- * src/ra_log_segments.erl:745-761), grouping (take_group, :911-950), file I/O, renames, symlinks and compaction
- * markers stay with the caller.
+ * src/ra_log_segments.erl:745-761) and grouping (take_group, :911-950) are the host helpers of "major compaction
+ * for many members in one call" below.  File I/O, renames, symlinks and compaction markers stay with the caller.
  *
  * All sources of a group lie in ONE files buffer; the live indexes of all sources in ONE list of (first, last) pairs
  * of uint64_t (2 * n_live values), each source owning a slice of it.  Within a slice the pairs are ascending and
@@ -334,6 +334,125 @@ int rgb_segment_compact_device(rgb_ctx *ctx, const rgb_seg_source *sources, uint
 int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, uint32_t n_sources, const void *files,
                         uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size, uint32_t flags,
                         void *out, uint64_t out_bytes, rgb_seg_compact_result *result);
+
+/* ==== major compaction for many members in one call: the plan, and the batched copy ====================
+ *
+ * A snapshot or a released cursor makes many members of a node compact at once, each with a few small groups.  The
+ * calls below serve all of them together: three pure host helpers restate the plan of major_compaction/3 -- which
+ * live indexes belong to which file, which files form a group -- and one device call copies ANY number of groups of
+ * ANY number of sources, each group failing on its own.  Between the plan and the copy the caller writes its
+ * .compaction_group markers (src/ra_log_segments.erl:783-786); renames, symlinks, deletes and sync_dir stay with the
+ * caller too.
+ *
+ * rgb_segment_compact_select: the fold of major_compaction/3 (src/ra_log_segments.erl:745-761) and of
+ * minor_compaction/2 (:843-854) for M members.  A member owns a slice of `segrefs` -- (range_first, range_last) pairs
+ * of uint64_t in the order compactable_segrefs/2 gives them, newest first -- and a slice of `live`, pairs in the form
+ * described above (live_n = 0: an empty or undefined sequence).  Per segref, in slice order: its selection is the
+ * member's live indexes inside {Start, min(End, ceiling)} (ra_seq:in_range/2 over the progressively limited Live);
+ * `ceiling` starts unbounded and drops to min(ceiling, End) only behind a segref whose selection was not empty
+ * (ra_seq:limit/2); an empty selection leaves Live as it was.  Nothing is assumed about the order of the ranges: what
+ * the reference's fold gives for overlapping or ascending ranges is what comes out.  A segref with
+ * range_first > range_last selects nothing (the reference's `undefined` range).
+ *
+ * picks[k] (one row per segref): the selection as pairs live_first .. live_first + live_n of `live_out`, clipped to
+ * the effective range; num_live = ra_seq:length of it (saturating at 2^64 - 1); flags = RGB_SEG_PICK_UNREFERENCED when
+ * it is empty -- exactly the Delete list of both compaction kinds.  The rows of the segrefs that members name are
+ * written (a row of a segref that no member's slice names is NOT written at all: it keeps what the caller put there),
+ * the pairs of `live_out` back to back in segref order, so picks[k].live_first / live_n are a source's live_first /
+ * live_n as they are.  *n_live_out = the pairs written.  Segrefs whose ranges do not overlap never need more than
+ * n_live + n_segrefs pairs; picks = NULL and live_out = NULL is the sizing form: nothing but the exact *n_live_out.
+ * RGB_E_INVAL, nothing written: a slice outside its list, segref slices not ascending by segref_first or not
+ * disjoint, live pairs not ascending / adjacent / first > last, more than live_out_cap (or 2^32 - 1) pairs. */
+typedef struct rgb_seg_member {
+  uint32_t segref_first, segref_n;   /* pairs segref_first .. segref_first + segref_n of `segrefs`, newest first */
+  uint32_t live_first, live_n;       /* pairs live_first .. live_first + live_n of `live` */
+} rgb_seg_member;
+
+typedef struct rgb_seg_pick {
+  uint64_t num_live;
+  uint32_t live_first, live_n;       /* in live_out */
+  uint32_t flags;                    /* RGB_SEG_PICK_UNREFERENCED or 0 */
+  uint32_t _pad;
+} rgb_seg_pick;
+#define RGB_SEG_PICK_UNREFERENCED 1u
+
+int rgb_segment_compact_select(const rgb_seg_member *members, uint32_t n_members, const uint64_t *segrefs,
+                               uint32_t n_segrefs, const uint64_t *live, uint32_t n_live, rgb_seg_pick *picks,
+                               uint64_t *live_out, uint32_t live_out_cap, uint32_t *n_live_out);
+
+/* rgb_segment_compact_take_groups: compaction_groups/3 with take_group/3 (src/ra_log_segments.erl:901-950) per
+ * member.  A member owns the slice src_first .. src_first + src_n of `infos` and `num_live`: its compactable sources
+ * OLDEST first (the order the fold's reversal produces), each with its info row (rgb_segment_info with the source's
+ * selection as the live list) and NumLive = ra_seq:length of that selection -- the length of the slice, not the number
+ * of live records found.  group_of[s] = the ordinal of the source's group within its member, counted from 0 in the
+ * order the groups are taken, or RGB_SEG_GROUP_NONE for a source that is skipped (or that no member names);
+ * members[m].n_groups = the groups.
+ *
+ * A source is compactable iff NumLive / NumEnts < 0.5 orelse LiveSz / (Sz - IdxSz) < 0.5; the ratios are compared as
+ * integers (2 * NumLive < NumEnts), which is the float comparison exactly while both operands are below 2^53.
+ * Over the remaining budgets (MaxCnt - NumLive < 0 orelse MaxSz - LiveSz < 0) with nothing accumulated: the source is
+ * skipped; with a group accumulated: the group is closed and the source STAYS for the next one; not compactable with
+ * a group accumulated: the group is closed and the source is dropped.  The budgets start again with every group.
+ * NumEnts == 0, and Sz - IdxSz == 0 when the first test was false (orelse), are badarith in the reference: the member
+ * gets status RGB_SEG_TAKE_BADARITH, no groups and RGB_SEG_GROUP_NONE throughout; other members are unaffected.
+ * RGB_E_INVAL, nothing written: a slice outside n_sources, slices not ascending by src_first or not disjoint. */
+typedef struct rgb_seg_take_member {
+  uint32_t src_first, src_n;         /* in */
+  uint32_t n_groups, status;         /* out: RGB_SEG_TAKE_OK / RGB_SEG_TAKE_BADARITH */
+} rgb_seg_take_member;
+#define RGB_SEG_TAKE_OK       0u
+#define RGB_SEG_TAKE_BADARITH 1u
+#define RGB_SEG_GROUP_NONE    0xFFFFFFFFu
+
+int rgb_segment_compact_take_groups(rgb_seg_take_member *members, uint32_t n_members, const rgb_seg_info *infos,
+                                    const uint64_t *num_live, uint32_t n_sources, uint64_t max_count, uint64_t max_size,
+                                    uint32_t *group_of);
+
+/* One compaction group of a batched call: the sources src_first .. src_first + src_n of the call's `sources`, oldest
+ * first, and the bytes of `out` its image may use.  Groups own disjoint, ascending slices of `sources` (a file that
+ * belongs to two groups is named by two sources); a source no group names is not copied from.  The live slices of
+ * the sources that groups name are either the same from their first pair on (the same live_first) or disjoint: a pair
+ * of the live list that two such sources reach from different live_first is RGB_E_INVAL for the call (its rank within
+ * its source is kept per pair). */
+typedef struct rgb_seg_group {
+  uint32_t src_first, src_n;
+  uint64_t out_offset;               /* the image = out[out_offset .. out_offset + file_bytes), any byte offset */
+  uint64_t out_bytes;                /* SPACE is tested against this */
+} rgb_seg_group;
+
+/* Host helper, pure: validates groups, sources and live slices as the calls below do and lays the images out back to
+ * back without padding: groups[g].out_offset and out_bytes = 8 + 32 * MaxCount_g + the sum of the group's sources'
+ * n_bytes are FILLED IN, *total_out = their sum, max_counts[g] (NULL: not wanted) = MaxCount_g.  A group with
+ * MaxCount > 65535 is RGB_E_INVAL for the call, as rgb_segment_compact_bound treats it; a group of no sources or no
+ * live indexes is legal: its image is the 8-byte header.  No cap on sources or groups beyond uint32_t (and
+ * 2^32 - 257 live indexes in all). */
+int rgb_segment_compact_groups_bound(rgb_seg_group *groups, uint32_t n_groups, const rgb_seg_source *sources,
+                                     uint32_t n_sources, const uint64_t *live, uint32_t n_live, uint64_t files_bytes,
+                                     uint64_t *total_out, uint32_t *max_counts);
+
+/* The batched copy.  Per group g: d_out[out_offset_g ..) and d_results[g] (rgb_seg_compact_result rows in device
+ * memory) are EXACTLY what rgb_segment_compact_device gives for that group alone with out_bytes_g -- every status,
+ * the precedence documented above, `source` counted within the group, the source's stored Crc, an index live in two
+ * sources copied twice.  A group that fails leaves its neighbours' images and rows as they are; its own output bytes
+ * are unspecified.  `groups`, `sources` and `live` are HOST arrays, validated before anything is enqueued
+ * (RGB_E_INVAL: what rgb_segment_compact_groups_bound refuses, a group's out range outside out_bytes, out ranges that
+ * overlap, unknown flags, NULLs).  RGB_SEG_COMPACT_VERIFY is the only flag.
+ *
+ * Launches: resolve (one workgroup per source), place (one lane per group: the walk of the single-group call, the
+ * row, and the 8 header bytes of a good image), copy (GROUP lanes per plan entry across all groups; the width is
+ * chosen once per call from the mean of the sources' bytes per live index), finish (VERIFY: the first mismatch in
+ * copy order PER GROUP).  The scratch plan is sized from the call and kept in the context: one such call per context
+ * at a time.  Only an image's own bytes are written, whatever the alignment of d_out and of the offsets. */
+int rgb_segment_compact_groups_device(rgb_ctx *ctx, const rgb_seg_group *groups, uint32_t n_groups,
+                                      const rgb_seg_source *sources, uint32_t n_sources, const void *d_files,
+                                      uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size,
+                                      uint32_t flags, void *d_out, uint64_t out_bytes, void *d_results, void *stream);
+/* Host-buffer form: synchronises; results[g] as above (a source with a bad header is BAD_SOURCE of its group here
+ * too: a batch across members survives one bad file); of `out` only the good images' own bytes are written. */
+int rgb_segment_compact_groups(rgb_ctx *ctx, const rgb_seg_group *groups, uint32_t n_groups,
+                               const rgb_seg_source *sources, uint32_t n_sources, const void *files, uint64_t files_bytes,
+                               const uint64_t *live, uint32_t n_live, uint64_t max_size, uint32_t flags, void *out,
+                               uint64_t out_bytes, rgb_seg_compact_result *results);
 
 /* ==== mem-table flush: the entries of many writers appended to their segment files in one call ==========
  *

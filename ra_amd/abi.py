@@ -176,6 +176,16 @@ assert (SEG_SOURCE_DTYPE.itemsize, SEG_INFO_DTYPE.itemsize, SEG_COMPACT_RESULT_D
  SEG_COMPACT_BAD_SOURCE) = range(7)
 SEG_COMPACT_VERIFY = 1
 SEG_COMPACT_MAX_SOURCES = 256
+# major compaction for many members (same header): the plan's descriptors and a group of the batched copy
+SEG_MEMBER_DTYPE = np.dtype([("segref_first", u32), ("segref_n", u32), ("live_first", u32), ("live_n", u32)])
+SEG_PICK_DTYPE = np.dtype([("num_live", u64), ("live_first", u32), ("live_n", u32), ("flags", u32), ("_pad", u32)])
+SEG_TAKE_MEMBER_DTYPE = np.dtype([("src_first", u32), ("src_n", u32), ("n_groups", u32), ("status", u32)])
+SEG_GROUP_DTYPE = np.dtype([("src_first", u32), ("src_n", u32), ("out_offset", u64), ("out_bytes", u64)])
+assert (SEG_MEMBER_DTYPE.itemsize, SEG_PICK_DTYPE.itemsize, SEG_TAKE_MEMBER_DTYPE.itemsize,
+        SEG_GROUP_DTYPE.itemsize) == (16, 24, 16, 24)
+SEG_PICK_UNREFERENCED = 1
+SEG_TAKE_OK, SEG_TAKE_BADARITH = 0, 1
+SEG_GROUP_NONE = 0xFFFFFFFF
 # mem-table flush (same header): one writer of a call, one run of appended entries in one file, the result
 SEG_WRITER_DTYPE = np.dtype([("entry_first", u32), ("entry_n", u32), ("open_count", u32), ("open_max_count", u32),
                              ("open_data_bytes", u64), ("range_first", u64), ("range_last", u64), ("_pad", u64)])

@@ -795,6 +795,159 @@ static ERL_NIF_TERM nif_segment_compact(ErlNifEnv *env, int argc, const ERL_NIF_
   return enif_make_tuple2(env, enif_make_atom(env, "error"), why);
 }
 
+/* One file of a member in SegrefsBin (32 bytes, little endian): where it lies in FilesBin and its segref range. */
+typedef struct nif_segref { uint64_t offset, n_bytes, range_first, range_last; } nif_segref;
+/* One row of RowsBin per segref (32 bytes): the selection (pairs live_first .. live_first + live_n of LiveOutBin),
+ * flags 1 = unreferenced, the file's group in GroupsBin (16#FFFFFFFF: none), the member's status (1 = badarith). */
+typedef struct nif_plan_row { uint64_t num_live; uint32_t live_first, live_n, flags, group, status, _pad; } nif_plan_row;
+
+/* segment_compact_plan(Ctx, MembersBin, SegrefsBin, FilesBin, LiveBin, MaxCount, MaxSize) ->
+ * {ok, RowsBin, GroupsBin, LiveOutBin}: the plan of major_compaction/3 for many members (src/ra_log_segments.erl:
+ * 745-761, 901-950): rgb_segment_compact_select, info/2 of every referenced file in chunks of at most 256, and
+ * rgb_segment_compact_take_groups.  MembersBin = rgb_seg_member records (segref_first:32, segref_n:32, live_first:32,
+ * live_n:32), a member's segrefs newest first.  GroupsBin = rgb_seg_group records laid out back to back by
+ * rgb_segment_compact_groups_bound over the sources in plan order: group by group, the group's files oldest first
+ * (a member's segrefs with that group number, last to first).  info/2 is the host-buffer rgb_segment_info: FilesBin is
+ * staged once per chunk, and a referenced file with a damaged header is {error, invalid} for the whole call, every
+ * member included (the copy fails only that file's group). */
+static ERL_NIF_TERM nif_segment_compact_plan(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary mb, sr, f, l, rows_bin, groups_bin, live_bin; uint64_t max_count, max_size;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &mb) || !enif_inspect_binary(env, argv[2], &sr) ||
+      !enif_inspect_binary(env, argv[3], &f) || !enif_inspect_binary(env, argv[4], &l) ||
+      !enif_get_uint64(env, argv[5], &max_count) || !enif_get_uint64(env, argv[6], &max_size) ||
+      mb.size % sizeof(rgb_seg_member) != 0 || sr.size % sizeof(nif_segref) != 0 || l.size % 16u != 0 ||
+      mb.size / sizeof(rgb_seg_member) > 0xFFFFFFFFu || sr.size / sizeof(nif_segref) > 0xFFFFFFFFu ||
+      l.size / 16u > 0xFFFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n_members = (uint32_t)(mb.size / sizeof(rgb_seg_member)), n_refs = (uint32_t)(sr.size / sizeof(nif_segref));
+  const uint32_t n_live = (uint32_t)(l.size / 16u);
+  const rgb_seg_member *members = (const rgb_seg_member *)mb.data;
+  const nif_segref *refs = (const nif_segref *)sr.data;
+  const uint64_t *live = n_live ? (const uint64_t *)l.data : NULL;
+  int rc = RGB_E_NOMEM;
+  uint32_t n_out = 0, n_cand = 0, n_groups = 0, n_src = 0;
+  uint64_t *ranges = (uint64_t *)enif_alloc((size_t)(n_refs ? n_refs : 1) * 16u);
+  rgb_seg_pick *picks = (rgb_seg_pick *)enif_alloc((size_t)(n_refs ? n_refs : 1) * sizeof(rgb_seg_pick));
+  rgb_seg_source *cand = (rgb_seg_source *)enif_alloc((size_t)(n_refs ? n_refs : 1) * sizeof(rgb_seg_source));
+  rgb_seg_source *srcs = (rgb_seg_source *)enif_alloc((size_t)(n_refs ? n_refs : 1) * sizeof(rgb_seg_source));
+  rgb_seg_info *infos = (rgb_seg_info *)enif_alloc((size_t)(n_refs ? n_refs : 1) * sizeof(rgb_seg_info));
+  uint64_t *num_live = (uint64_t *)enif_alloc((size_t)(n_refs ? n_refs : 1) * 8u);
+  uint32_t *ref_of = (uint32_t *)enif_alloc((size_t)(n_refs ? n_refs : 1) * 4u);      /* candidate -> segref */
+  uint32_t *group_of = (uint32_t *)enif_alloc((size_t)(n_refs ? n_refs : 1) * 4u);
+  rgb_seg_take_member *take = (rgb_seg_take_member *)enif_alloc((size_t)(n_members ? n_members : 1) * sizeof(rgb_seg_take_member));
+  rgb_seg_group *groups = (rgb_seg_group *)enif_alloc((size_t)(n_refs ? n_refs : 1) * sizeof(rgb_seg_group));
+  uint64_t *live_out = NULL;
+  int have_bins = 0;
+  if (!ranges || !picks || !cand || !srcs || !infos || !num_live || !ref_of || !group_of || !take || !groups) goto done;
+  for (uint32_t k = 0; k < n_refs; ++k) { ranges[2 * k] = refs[k].range_first; ranges[2 * k + 1] = refs[k].range_last; }
+  memset(picks, 0, (size_t)n_refs * sizeof(rgb_seg_pick));
+  if ((rc = rgb_segment_compact_select(members, n_members, ranges, n_refs, live, n_live, NULL, NULL, 0, &n_out))) goto done;
+  live_out = (uint64_t *)enif_alloc((size_t)(n_out ? n_out : 1) * 16u);
+  if (!live_out) { rc = RGB_E_NOMEM; goto done; }
+  if ((rc = rgb_segment_compact_select(members, n_members, ranges, n_refs, live, n_live, picks, live_out, n_out, &n_out)))
+    goto done;
+  /* the candidates of every member oldest first (the fold prepends), info/2 with the selection as the live list */
+  for (uint32_t m = 0; m < n_members; ++m) {
+    take[m].src_first = n_cand; take[m].n_groups = 0; take[m].status = 0;
+    for (uint32_t k = members[m].segref_n; k-- > 0u;) {
+      const uint32_t r = members[m].segref_first + k;
+      if (picks[r].flags & RGB_SEG_PICK_UNREFERENCED) continue;
+      rgb_seg_source s; memset(&s, 0, sizeof s);
+      s.offset = refs[r].offset; s.n_bytes = refs[r].n_bytes; s.live_first = picks[r].live_first; s.live_n = picks[r].live_n;
+      cand[n_cand] = s; num_live[n_cand] = picks[r].num_live; ref_of[n_cand] = r;
+      n_cand += 1;
+    }
+    take[m].src_n = n_cand - take[m].src_first;
+  }
+  for (uint32_t lo = 0; lo < n_cand; lo += RGB_SEG_COMPACT_MAX_SOURCES) {
+    const uint32_t n = n_cand - lo < RGB_SEG_COMPACT_MAX_SOURCES ? n_cand - lo : RGB_SEG_COMPACT_MAX_SOURCES;
+    if ((rc = rgb_segment_info(c->ctx, cand + lo, n, f.data, f.size, live_out, n_out, infos + lo))) goto done;
+  }
+  if ((rc = rgb_segment_compact_take_groups(take, n_members, infos, num_live, n_cand, max_count, max_size, group_of))) goto done;
+  rc = RGB_E_NOMEM;
+  if (!enif_alloc_binary((size_t)n_refs * sizeof(nif_plan_row), &rows_bin)) goto done;
+  nif_plan_row *rows = (nif_plan_row *)rows_bin.data;
+  for (uint32_t r = 0; r < n_refs; ++r) {
+    nif_plan_row row; memset(&row, 0, sizeof row);
+    row.num_live = picks[r].num_live; row.live_first = picks[r].live_first; row.live_n = picks[r].live_n;
+    row.flags = picks[r].flags; row.group = RGB_SEG_GROUP_NONE;
+    rows[r] = row;
+  }
+  for (uint32_t m = 0; m < n_members; ++m) {
+    for (uint32_t k = 0; k < members[m].segref_n; ++k) rows[members[m].segref_first + k].status = take[m].status;
+    for (uint32_t g = 0; g < take[m].n_groups; ++g) {
+      rgb_seg_group gr; memset(&gr, 0, sizeof gr);
+      gr.src_first = n_src;
+      for (uint32_t j = 0; j < take[m].src_n; ++j) {
+        const uint32_t q = take[m].src_first + j;
+        if (group_of[q] != g) continue;
+        srcs[n_src++] = cand[q];
+        rows[ref_of[q]].group = n_groups;
+      }
+      gr.src_n = n_src - gr.src_first;
+      groups[n_groups++] = gr;
+    }
+  }
+  uint64_t total = 0;
+  if ((rc = rgb_segment_compact_groups_bound(groups, n_groups, srcs, n_src, live_out, n_out, f.size, &total, NULL))) {
+    enif_release_binary(&rows_bin);
+    goto done;
+  }
+  rc = RGB_E_NOMEM;
+  if (!enif_alloc_binary((size_t)n_groups * sizeof(rgb_seg_group), &groups_bin)) { enif_release_binary(&rows_bin); goto done; }
+  if (!enif_alloc_binary((size_t)n_out * 16u, &live_bin)) {
+    enif_release_binary(&rows_bin); enif_release_binary(&groups_bin);
+    goto done;
+  }
+  if (n_groups) memcpy(groups_bin.data, groups, (size_t)n_groups * sizeof(rgb_seg_group));
+  if (n_out) memcpy(live_bin.data, live_out, (size_t)n_out * 16u);
+  have_bins = 1;
+  rc = RGB_OK;
+done:
+  {
+    void *blocks[] = {ranges, picks, cand, srcs, infos, num_live, ref_of, group_of, take, groups, live_out};
+    for (size_t i = 0; i < sizeof blocks / sizeof blocks[0]; ++i)
+      if (blocks[i]) enif_free(blocks[i]);
+  }
+  if (rc || !have_bins) return mk_error(env, c, rc ? rc : RGB_E_NOMEM);
+  return enif_make_tuple4(env, enif_make_atom(env, "ok"), enif_make_binary(env, &rows_bin),
+                          enif_make_binary(env, &groups_bin), enif_make_binary(env, &live_bin));
+}
+
+/* segment_compact_groups(Ctx, GroupsBin, SourcesBin, FilesBin, LiveBin, MaxSize, Flags) -> {ok, ResultsBin, OutBin}:
+ * the copy of every group of a plan in one call (rgb_segment_compact_groups).  ResultsBin = one rgb_seg_compact_result
+ * per group; OutBin = the output buffer up to the end of the last group's range: a group whose status is 0 has its
+ * image at its out_offset (file_bytes bytes), the bytes of every other range are zeros. */
+static ERL_NIF_TERM nif_segment_compact_groups(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary g, s, f, l, res, out; uint64_t max_size; unsigned flags;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &g) || !enif_inspect_binary(env, argv[2], &s) ||
+      !enif_inspect_binary(env, argv[3], &f) || !enif_inspect_binary(env, argv[4], &l) ||
+      !enif_get_uint64(env, argv[5], &max_size) || !enif_get_uint(env, argv[6], &flags) ||
+      g.size % sizeof(rgb_seg_group) != 0 || s.size % sizeof(rgb_seg_source) != 0 || l.size % 16u != 0 ||
+      g.size / sizeof(rgb_seg_group) > 0xFFFFFFFFu || s.size / sizeof(rgb_seg_source) > 0xFFFFFFFFu ||
+      l.size / 16u > 0xFFFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n_groups = (uint32_t)(g.size / sizeof(rgb_seg_group)), n_src = (uint32_t)(s.size / sizeof(rgb_seg_source));
+  const uint32_t n_live = (uint32_t)(l.size / 16u);
+  const rgb_seg_group *groups = (const rgb_seg_group *)g.data;
+  uint64_t room = 0;
+  for (uint32_t k = 0; k < n_groups; ++k) {
+    const uint64_t end = groups[k].out_offset + groups[k].out_bytes;
+    if (end < groups[k].out_offset || end > ((uint64_t)1 << 40)) return mk_error(env, c, RGB_E_INVAL);
+    if (end > room) room = end;
+  }
+  if (!enif_alloc_binary((size_t)n_groups * sizeof(rgb_seg_compact_result), &res)) return mk_error(env, c, RGB_E_NOMEM);
+  if (!enif_alloc_binary((size_t)room, &out)) { enif_release_binary(&res); return mk_error(env, c, RGB_E_NOMEM); }
+  memset(out.data, 0, (size_t)room);
+  int rc = rgb_segment_compact_groups(c->ctx, groups, n_groups, (const rgb_seg_source *)s.data, n_src, f.data, f.size,
+                                      n_live ? (const uint64_t *)l.data : NULL, n_live, max_size, flags, out.data, room,
+                                      (rgb_seg_compact_result *)res.data);
+  if (rc) { enif_release_binary(&res); enif_release_binary(&out); return mk_error(env, c, rc); }
+  return enif_make_tuple3(env, enif_make_atom(env, "ok"), enif_make_binary(env, &res), enif_make_binary(env, &out));
+}
+
 /* segment_flush(Ctx, WritersBin, EntriesBin, DataBin, MaxCount, MaxSize, Flags) -> {ok, PiecesBin, OutBin} |
  * {error, _}: the mem-table flush of every writer of a WAL file in one call (flush_mem_table_ranges/2 and
  * append_to_segment/6, src/ra_log_segment_writer.erl:268-329, 425-500; ra_log_segment:append/4, is_full/1 and flush/1,
@@ -966,6 +1119,8 @@ static ErlNifFunc nif_funcs[] = {
   {"segment_build", 5, nif_segment_build, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_info", 4, nif_segment_info, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_compact", 6, nif_segment_compact, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_compact_plan", 7, nif_segment_compact_plan, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"segment_compact_groups", 7, nif_segment_compact_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_flush", 7, nif_segment_flush, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_read", 5, nif_segment_read, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"crc32_spans", 3, nif_crc32_spans, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -686,6 +686,147 @@ __global__ void rgb_compact_finish_kernel(const plan_rec *__restrict__ plan, con
   __builtin_memcpy(result_v, &res, sizeof res);
 }
 
+/* ---- major compaction for many members (include/ra_gpu_wal.h, "... for many members in one call") ----------
+ * Any number of groups in one call.  resolve is rgb_compact_resolve_kernel as it is: its source numbers and plan bases
+ * are already global.  The three passes behind it, each its own launch:
+ *   place    one lane per group: the walk of rgb_compact_place_kernel over the group's own sources (byte bases within
+ *            the group), the group's header row and result row, and the 8 header bytes of a good image -- a header-only
+ *            group has no plan entry that could write them
+ *   copy     GROUP lanes per plan entry across all groups.  The entry's group is found from the groups' first plan
+ *            entries alone (a binary search: groups without entries share their first entry with their successor, and
+ *            the last of equals is the one that owns it) -- NOT from the plan record, which a failed group may have
+ *            left unwritten.  Record number = entry - the group's first entry.  Nothing for a group that is not OK.
+ *   finish   (VERIFY) one lane per group: the first mismatch of the group in copy order into a CRC status
+ * The kernels' parameter types are the unit's own (see "major compaction" above). */
+struct grp_desc { u64 out_offset, out_bytes; u32 src_first, src_n, plan_first, max_count; };   /* staged from the host */
+static_assert(sizeof(grp_desc) == 32, "");
+constexpr int GRP_LANES = 64;                           /* groups per workgroup of place and finish: one wavefront */
+
+__global__ __launch_bounds__(GRP_LANES) void rgb_cgroups_place_kernel(
+    const grp_desc *__restrict__ groups, u32 n_groups, const src_desc *__restrict__ srcs, const src_done *__restrict__ done,
+    const plan_rec *__restrict__ plan, u64 max_size, u64 *__restrict__ byte_base, work_hdr *__restrict__ hdrs,
+    unsigned char *__restrict__ out, void *results_v) {
+  const u32 g = blockIdx.x * GRP_LANES + threadIdx.x;
+  if (g >= n_groups) return;
+  const grp_desc gd = groups[g];
+  rgb_seg_compact_result res{};
+  u64 bytes = 0;
+  u32 recs = 0;
+  for (u32 q = 0; q < gd.src_n && !res.status; ++q)
+    if (done[gd.src_first + q].bad) { res.status = RGB_SEG_COMPACT_BAD_SOURCE; res.source = q; }
+  for (u32 q = 0; q < gd.src_n && !res.status; ++q) {
+    const u32 s = gd.src_first + q;
+    const src_done d = done[s];
+    const plan_rec *p = plan + srcs[s].plan_base;
+    /* as rgb_compact_place_kernel: the first k with more than max_size payload bytes of the GROUP in front of it */
+    u32 full_k = NONE32;
+    if (d.sel_count && bytes + p[d.sel_count - 1u].pre > max_size) {
+      u32 lo = 0, hi = d.sel_count - 1u;
+      while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (bytes + p[mid].pre > max_size) hi = mid; else lo = mid + 1u;
+      }
+      full_k = lo;
+    }
+    if (d.miss_k != NONE32 && d.miss_k <= d.trunc_k && d.miss_k <= full_k) {
+      res.status = RGB_SEG_COMPACT_MISSING; res.source = q; res.index = d.miss_idx;
+    } else if (d.trunc_k != NONE32 && d.trunc_k <= full_k) {
+      res.status = RGB_SEG_COMPACT_TRUNCATED; res.source = q; res.index = p[d.trunc_k].idx;
+    } else if (full_k != NONE32) {
+      res.status = RGB_SEG_COMPACT_FULL; res.source = q; res.index = p[full_k].idx;
+    } else {
+      byte_base[s] = bytes;
+      bytes += d.sel_bytes;
+      recs += d.sel_count;
+    }
+  }
+  if (!res.status) {
+    res.n_entries = recs;                               /* == max_count: every live index was found */
+    res.file_bytes = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * gd.max_count + bytes;
+    if (gd.out_bytes < res.file_bytes) { res.status = RGB_SEG_COMPACT_SPACE; res.n_entries = 0u; }
+  }
+  if (!res.status) put_header(out + gd.out_offset, gd.max_count);
+  work_hdr h{};
+  h.status = res.status; h.crc_fail = NONE32;
+  hdrs[g] = h;
+  __builtin_memcpy(reinterpret_cast<unsigned char *>(results_v) + sizeof(res) * (u64)g, &res, sizeof res);
+}
+
+/* the group that owns plan entry e: the last g with plan_first <= e (e < the entries of the call, so there is one) */
+__device__ __forceinline__ u32 group_of_entry(const grp_desc *groups, u32 n_groups, u32 e) {
+  u32 lo = 0, hi = n_groups;                            /* lo = groups whose plan_first <= e, at least one */
+  while (hi - lo > 1u) {
+    const u32 mid = (lo + hi) >> 1;
+    if (groups[mid].plan_first <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+template <int GROUP, bool VERIFY>
+__global__ __launch_bounds__(THREADS) void rgb_cgroups_copy_kernel(
+    const plan_rec *__restrict__ plan, u32 n, const grp_desc *__restrict__ groups, u32 n_groups,
+    const unsigned char *__restrict__ files, const u64 *__restrict__ byte_base, work_hdr *__restrict__ hdrs,
+    unsigned char *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) u32 lds[VERIFY ? LDS_WORDS : 4u];
+  if (VERIFY) load_tables<GROUP>(lds);
+  constexpr u32 PER_BLOCK = THREADS / GROUP;
+  const u32 lane = threadIdx.x & (GROUP - 1);
+  for (u32 base = blockIdx.x * PER_BLOCK; base < n; base += gridDim.x * PER_BLOCK) {
+    const u32 e = base + threadIdx.x / GROUP;
+    bool live = e < n;
+    u32 g = 0, rec = 0;
+    unsigned char *image = out;
+    u64 data_start = 0;
+    if (live) {
+      g = group_of_entry(groups, n_groups, e);
+      live = hdrs[g].status == RGB_SEG_COMPACT_OK;      /* decided before this launch: the same for the whole group */
+    }
+    plan_rec p{};
+    u64 dst_off = 0;
+    if (live) {
+      const grp_desc gd = groups[g];
+      p = plan[e];
+      rec = e - gd.plan_first;
+      image = out + gd.out_offset;
+      data_start = (u64)RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * gd.max_count;
+      dst_off = data_start + byte_base[p.src] + p.pre;
+    }
+    const u32 len = p.len;
+    const unsigned char *pay = files + p.src_off;
+    unsigned char *dst = image + dst_off;
+    const bool wide = live && len >= 16u;
+    u32 crc = 0;
+    if (VERIFY) crc = entry_crc<GROUP, true>(lds, pay, dst, len, live, lane);
+    else if (wide) copy_plain<GROUP>(pay, dst, len, lane);
+    if (live && lane == 0u) {
+      if (VERIFY) crc = lane0_crc<true>(lds, crc, pay, dst, len);
+      else if (!wide) for (u32 k = 0; k < len; ++k) dst[k] = pay[k];
+      if (VERIFY && p.crc != 0u && crc != p.crc) atomic_min(&hdrs[g].crc_fail, rec);
+      /* the source's Crc, 0 included */
+      put_record(image + RGB_SEG_HEADER_BYTES + (u64)RGB_SEG_RECORD_BYTES * rec, p.idx, p.term, dst_off, len, p.crc);
+    }
+  }
+}
+
+/* VERIFY: per group the first mismatch in copy order, once every workgroup of the copy is done */
+__global__ __launch_bounds__(GRP_LANES) void rgb_cgroups_finish_kernel(
+    const grp_desc *__restrict__ groups, u32 n_groups, const plan_rec *__restrict__ plan,
+    const work_hdr *__restrict__ hdrs, void *results_v) {
+  const u32 g = blockIdx.x * GRP_LANES + threadIdx.x;
+  if (g >= n_groups) return;
+  const work_hdr h = hdrs[g];
+  if (h.status != RGB_SEG_COMPACT_OK || h.crc_fail == NONE32) return;
+  const plan_rec *p = plan + groups[g].plan_first + h.crc_fail;
+  unsigned char *row = reinterpret_cast<unsigned char *>(results_v) + sizeof(rgb_seg_compact_result) * (u64)g;
+  rgb_seg_compact_result res;
+  __builtin_memcpy(&res, row, sizeof res);
+  res.status = RGB_SEG_COMPACT_CRC;
+  res.n_entries = 0u;
+  res.source = p->src - groups[g].src_first;
+  res.index = p->idx;
+  __builtin_memcpy(row, &res, sizeof res);
+}
+
 /* ---- reading entries back (include/ra_gpu_wal.h, "reading entries back") -----------------------------------
  * Passes, each its own launch, so that no workgroup ever waits for another:
  *   resolve  one workgroup per source: the walk and the effective records as in compaction (walk_effective), the
@@ -1982,6 +2123,156 @@ extern "C" int rgb_segment_compact(rgb_ctx *ctx, const rgb_seg_source *sources, 
   return seg::fetch_result(result, s.result, RGB_SEG_COMPACT_OK, st, [&](const rgb_seg_compact_result &res) {
     return seg::copy_down(out, s.out, (size_t)res.file_bytes, st);
   });
+}
+
+/* ---- major compaction for many members: any number of groups in one call ---------------------------------- */
+
+extern "C" int rgb_seg_compact_groups_check(const rgb_seg_group *groups, uint32_t n_groups, const rgb_seg_source *sources,
+                                            uint32_t n_sources, const uint64_t *live, uint32_t n_live, uint64_t files_bytes,
+                                            int with_out, uint64_t out_bytes, uint32_t *order, uint32_t *asked,
+                                            uint32_t *group_of_src, uint32_t *rank, uint32_t *max_counts,
+                                            uint64_t *sum_bytes, uint64_t *total_count);
+
+extern "C" int rgb_segment_compact_groups_device(rgb_ctx *ctx, const rgb_seg_group *groups, uint32_t n_groups,
+                                                 const rgb_seg_source *sources, uint32_t n_sources, const void *d_files,
+                                                 uint64_t files_bytes, const uint64_t *live, uint32_t n_live,
+                                                 uint64_t max_size, uint32_t flags, void *d_out, uint64_t out_bytes,
+                                                 void *d_results, void *stream) {
+  if (!ctx || (n_groups && (!groups || !d_out || !d_results)) || (n_sources && !sources) || (files_bytes && !d_files) ||
+      (n_live && !live) || (flags & ~RGB_SEG_COMPACT_VERIFY))
+    return RGB_E_INVAL;
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)rgb_ctx_stream(ctx);
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  /* the pinned block: what goes up (sources, groups, live list, ranks), and behind it the host's own tables */
+  const size_t off_grps = (size_t)n_sources * sizeof(seg::src_desc);
+  const size_t off_live = off_grps + (size_t)n_groups * sizeof(seg::grp_desc);
+  const size_t off_rank = off_live + (size_t)n_live * 16u;
+  const size_t need = seg::up16(off_rank + (size_t)n_live * 4u) + 16u;
+  const size_t off_asked = need, off_order = off_asked + (size_t)n_sources * 4u, off_counts = off_order + (size_t)n_groups * 4u;
+  seg::pinned_upload &up = s.compact_desc;
+  int rc = up.prepare(off_counts + (size_t)n_groups * 4u + 16u);
+  if (rc) return rc;
+  unsigned char *h = (unsigned char *)up.h;
+  seg::src_desc *h_srcs = (seg::src_desc *)h;
+  seg::grp_desc *h_grps = (seg::grp_desc *)(h + off_grps);
+  uint32_t *h_asked = (uint32_t *)(h + off_asked), *h_counts = (uint32_t *)(h + off_counts);
+  uint64_t sum = 0, total = 0;
+  rc = rgb_seg_compact_groups_check(groups, n_groups, sources, n_sources, live, n_live, files_bytes, 1, out_bytes,
+                                    (uint32_t *)(h + off_order), h_asked, nullptr, (uint32_t *)(h + off_rank), h_counts,
+                                    &sum, &total);
+  if (rc) return rc;
+  if (n_groups == 0) return RGB_OK;
+  seg::u32 plan_base = 0;
+  for (seg::u32 i = 0; i < n_sources; ++i) {            /* (a source no group names asks for nothing) */
+    seg::src_desc d;
+    d.offset = sources[i].offset; d.n_bytes = sources[i].n_bytes;
+    d.live_first = sources[i].live_first; d.live_n = sources[i].live_n;
+    d.asked = h_asked[i]; d.plan_base = plan_base;
+    if (!d.asked) { d.live_first = 0u; d.live_n = 0u; }
+    plan_base += d.asked;
+    h_srcs[i] = d;
+  }
+  for (seg::u32 g = 0; g < n_groups; ++g) {
+    seg::grp_desc d;
+    d.out_offset = groups[g].out_offset; d.out_bytes = groups[g].out_bytes;
+    d.src_first = groups[g].src_first; d.src_n = groups[g].src_n;
+    d.plan_first = 0u; d.max_count = h_counts[g];
+    h_grps[g] = d;
+  }
+  /* a group's first plan entry: that of its first source; without sources, its successor's (the end for the last) */
+  for (seg::u32 g = n_groups, behind = (seg::u32)total; g-- > 0u;) {
+    if (h_grps[g].src_n) behind = h_srcs[h_grps[g].src_first].plan_base;
+    h_grps[g].plan_first = behind;
+  }
+  if (n_live) memcpy(h + off_live, live, (size_t)n_live * 16u);
+  const size_t off_base = (size_t)n_sources * sizeof(seg::src_done);
+  const size_t off_hdr = seg::up16(off_base + (size_t)n_sources * 8u);
+  const size_t off_plan = off_hdr + (size_t)n_groups * sizeof(seg::work_hdr);
+  if (s.compact_work.reserve(off_plan + (size_t)total * sizeof(seg::plan_rec) + 16u)) return RGB_E_NOMEM;
+  if ((rc = up.upload(need, st))) return rc;
+  unsigned char *d = (unsigned char *)up.d.p, *w = (unsigned char *)s.compact_work.p;
+  const seg::src_desc *d_srcs = (const seg::src_desc *)d;
+  const seg::grp_desc *d_grps = (const seg::grp_desc *)(d + off_grps);
+  const seg::plan_rec *d_plan = (const seg::plan_rec *)(w + off_plan);
+  seg::u64 *d_base = (seg::u64 *)(w + off_base);
+  seg::work_hdr *d_hdrs = (seg::work_hdr *)(w + off_hdr);
+  (void)hipGetLastError();
+  if (n_sources)
+    hipLaunchKernelGGL(seg::rgb_compact_resolve_kernel, dim3(n_sources), dim3(seg::THREADS), 0, st, d_srcs,
+                       (const unsigned char *)d_files, (const seg::u64 *)(d + off_live), (const seg::u32 *)(d + off_rank),
+                       0u, (void *)nullptr, (seg::src_done *)w, (seg::plan_rec *)(w + off_plan));
+  const seg::u32 grp_grid = (n_groups + seg::GRP_LANES - 1u) / seg::GRP_LANES;
+  hipLaunchKernelGGL(seg::rgb_cgroups_place_kernel, dim3(grp_grid), dim3(seg::GRP_LANES), 0, st, d_grps, n_groups, d_srcs,
+                     (const seg::src_done *)w, d_plan, (seg::u64)max_size, d_base, d_hdrs, (unsigned char *)d_out,
+                     d_results);
+  const seg::u32 n = (seg::u32)total;
+  if (n == 0u) return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;     /* header-only images: place wrote them */
+  /* (the mean over the sources' bytes, as the single-group call) */
+  const seg::u32 width = seg::group_width(sum / n);
+  const bool verify = (flags & RGB_SEG_COMPACT_VERIFY) != 0u;
+  seg::with_width(width, [&](auto gw) {
+    constexpr int G = decltype(gw)::value;
+    auto *copy = verify ? seg::rgb_cgroups_copy_kernel<G, true> : seg::rgb_cgroups_copy_kernel<G, false>;
+    hipLaunchKernelGGL(copy, dim3(seg::entry_grid(n, width)), dim3(seg::THREADS), 0, st, d_plan, n, d_grps, n_groups,
+                       (const unsigned char *)d_files, (const seg::u64 *)d_base, d_hdrs, (unsigned char *)d_out);
+  });
+  if (verify)
+    hipLaunchKernelGGL(seg::rgb_cgroups_finish_kernel, dim3(grp_grid), dim3(seg::GRP_LANES), 0, st, d_grps, n_groups,
+                       d_plan, (const seg::work_hdr *)d_hdrs, d_results);
+  return hipGetLastError() == hipSuccess ? RGB_OK : RGB_E_HIP;
+}
+
+extern "C" int rgb_segment_compact_groups(rgb_ctx *ctx, const rgb_seg_group *groups, uint32_t n_groups,
+                                          const rgb_seg_source *sources, uint32_t n_sources, const void *files,
+                                          uint64_t files_bytes, const uint64_t *live, uint32_t n_live, uint64_t max_size,
+                                          uint32_t flags, void *out, uint64_t out_bytes, rgb_seg_compact_result *results) {
+  if (!ctx || (n_groups && (!groups || !out || !results)) || (files_bytes && !files) ||
+      (flags & ~RGB_SEG_COMPACT_VERIFY))
+    return RGB_E_INVAL;
+  /* the device's copy of `out` ends with the last image: the room behind it is the caller's alone */
+  uint64_t room = 0;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    if (groups[g].out_offset > out_bytes || groups[g].out_bytes > out_bytes - groups[g].out_offset) return RGB_E_INVAL;
+    if (groups[g].out_offset + groups[g].out_bytes > room) room = groups[g].out_offset + groups[g].out_bytes;
+  }
+  std::vector<uint32_t> order(n_groups ? n_groups : 1u);
+  int rc = rgb_seg_compact_groups_check(groups, n_groups, sources, n_sources, live, n_live, files_bytes, 1, out_bytes,
+                                        order.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  if (n_groups == 0) return RGB_OK;
+  if (hipSetDevice(rgb_ctx_device(ctx)) != hipSuccess) return RGB_E_HIP;
+  std::lock_guard<std::recursive_mutex> lk(seg::g_mu);
+  seg::stage &s = seg::g_stages[ctx];
+  hipStream_t st = (hipStream_t)rgb_ctx_stream(ctx);
+  const size_t rows = (size_t)n_groups * sizeof(rgb_seg_compact_result);
+  if (s.out.reserve((size_t)room + 16u) || s.result.reserve(rows)) return RGB_E_NOMEM;
+  if ((rc = seg::stage_in(s.data, files, (size_t)files_bytes, st))) return rc;
+  rc = rgb_segment_compact_groups_device(ctx, groups, n_groups, sources, n_sources, s.data.p, files_bytes, live, n_live,
+                                         max_size, flags, s.out.p, room, s.result.p, st);
+  if (rc) return rc;
+  std::vector<rgb_seg_compact_result> got(n_groups);
+  if ((rc = seg::fetch(got.data(), s.result, rows, st))) return rc;
+  /* only the good images' own bytes come back; neighbours that touch travel in one piece */
+  uint64_t run_first = 0, run_end = 0;
+  auto flush = [&]() -> int {
+    if (run_end == run_first) return RGB_OK;
+    return hipMemcpyAsync((unsigned char *)out + run_first, (const unsigned char *)s.out.p + run_first,
+                          (size_t)(run_end - run_first), hipMemcpyDeviceToHost, st) == hipSuccess ? RGB_OK : RGB_E_HIP;
+  };
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    if (got[g].status != RGB_SEG_COMPACT_OK) continue;
+    const uint64_t first = groups[g].out_offset, end = first + got[g].file_bytes;
+    if (first != run_end || run_end == run_first) {
+      if ((rc = flush())) return rc;
+      run_first = first;
+    }
+    run_end = end;
+  }
+  if ((rc = flush())) return rc;
+  if (hipStreamSynchronize(st) != hipSuccess) return RGB_E_HIP;
+  memcpy(results, got.data(), rows);
+  return RGB_OK;
 }
 
 /* ---- mem-table flush: the entries of many writers into their segment files ------------------------------ */

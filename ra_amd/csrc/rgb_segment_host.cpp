@@ -4,6 +4,7 @@
  * group, of a mem-table flush, of a batched read and of the snapshot calls.  No HIP here, so the file also builds on
  * its own under the sanitizers (tests/test_segment.py::test_segment_scan_under_sanitizers,
  * tests/test_segment_compact.py::test_compact_descriptors_under_sanitizers,
+ * tests/test_segment_compact_groups.py::test_plan_helpers_under_sanitizers,
  * tests/test_segment_flush.py::test_flush_descriptors_under_sanitizers,
  * tests/test_segment_read.py::test_read_descriptors_under_sanitizers,
  * tests/test_snapshot_files.py::test_snapshot_descriptors_under_sanitizers).
@@ -79,6 +80,281 @@ extern "C" int rgb_segment_compact_bound(const rgb_seg_source *sources, uint32_t
   if (sum + head < sum) return RGB_E_INVAL;
   *bound_out = head + sum;
   *max_count_out = max_count;
+  return RGB_OK;
+}
+
+/* ---- major compaction for many members: the plan (pure), and the descriptors of the batched copy ---------- */
+
+namespace {
+/* pairs [first, first + n) of `live`: ascending, not adjacent, first <= last */
+inline bool pairs_ok(const uint64_t *live, uint32_t first, uint32_t n) {
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint64_t i = (uint64_t)first + k;
+    const uint64_t a = live[2 * i], b = live[2 * i + 1];
+    if (a > b) return false;
+    if (k) {
+      const uint64_t prev_last = live[2 * i - 1];
+      if (a <= prev_last || a - prev_last < 2u) return false;
+    }
+  }
+  return true;
+}
+/* the pairs of the slice that meet {lo, hi}: [*from, *to), by two binary searches */
+inline void pairs_in(const uint64_t *live, uint32_t first, uint32_t n, uint64_t lo, uint64_t hi, uint32_t *from,
+                     uint32_t *to) {
+  uint32_t a = 0, b = n;                                 /* a = pairs whose last < lo */
+  while (a < b) {
+    const uint32_t mid = a + (b - a) / 2u;
+    if (live[2 * ((uint64_t)first + mid) + 1] < lo) a = mid + 1u; else b = mid;
+  }
+  *from = a;
+  b = n;                                                 /* a = pairs whose first <= hi (not below *from) */
+  while (a < b) {
+    const uint32_t mid = a + (b - a) / 2u;
+    if (live[2 * ((uint64_t)first + mid)] <= hi) a = mid + 1u; else b = mid;
+  }
+  *to = a;
+}
+/* One pass of the fold over every member; write = false counts only.  -> the pairs the selections hold. */
+uint64_t select_pass(const rgb_seg_member *members, uint32_t n_members, const uint64_t *segrefs, const uint64_t *live,
+                     rgb_seg_pick *picks, uint64_t *live_out, bool write) {
+  uint64_t n_out = 0;
+  for (uint32_t m = 0; m < n_members; ++m) {
+    const rgb_seg_member &mb = members[m];
+    uint64_t ceiling = ~0ull;                            /* ra_seq:limit/2 so far: Live holds nothing above it */
+    for (uint32_t k = 0; k < mb.segref_n; ++k) {
+      const uint64_t r = (uint64_t)mb.segref_first + k;
+      const uint64_t start = segrefs[2 * r], end = segrefs[2 * r + 1];
+      const uint64_t top = end < ceiling ? end : ceiling;
+      uint32_t from = 0, to = 0;
+      if (start <= top) pairs_in(live, mb.live_first, mb.live_n, start, top, &from, &to);
+      if (write) {
+        rgb_seg_pick p{};
+        p.live_first = (uint32_t)n_out; p.live_n = to - from;
+        p.flags = to == from ? RGB_SEG_PICK_UNREFERENCED : 0u;
+        for (uint32_t j = from; j < to; ++j) {
+          const uint64_t i = (uint64_t)mb.live_first + j;
+          const uint64_t a = live[2 * i] < start ? start : live[2 * i], b = live[2 * i + 1] > top ? top : live[2 * i + 1];
+          live_out[2 * (n_out + (j - from))] = a;
+          live_out[2 * (n_out + (j - from)) + 1] = b;
+          const uint64_t len = b - a + 1u;               /* 0: the one range of 2^64 indexes */
+          p.num_live = (len == 0u || p.num_live + len < p.num_live) ? ~0ull : p.num_live + len;
+        }
+        picks[r] = p;
+      }
+      n_out += to - from;
+      if (to != from) ceiling = top;                     /* min(ceiling, End), and only behind a selection */
+    }
+  }
+  return n_out;
+}
+}  // namespace
+
+extern "C" int rgb_segment_compact_select(const rgb_seg_member *members, uint32_t n_members, const uint64_t *segrefs,
+                                          uint32_t n_segrefs, const uint64_t *live, uint32_t n_live, rgb_seg_pick *picks,
+                                          uint64_t *live_out, uint32_t live_out_cap, uint32_t *n_live_out) {
+  if (!n_live_out || (n_members && !members) || (n_segrefs && !segrefs) || (n_live && !live)) return RGB_E_INVAL;
+  const bool sizing = !picks && !live_out;
+  uint64_t next = 0;                                     /* the first segref a later slice may name */
+  for (uint32_t m = 0; m < n_members; ++m) {
+    const rgb_seg_member &mb = members[m];
+    if (mb.segref_first > n_segrefs || mb.segref_n > n_segrefs - mb.segref_first) return RGB_E_INVAL;
+    if (mb.segref_first < next) return RGB_E_INVAL;
+    next = (uint64_t)mb.segref_first + mb.segref_n;
+    if (mb.live_first > n_live || mb.live_n > n_live - mb.live_first) return RGB_E_INVAL;
+    if (!pairs_ok(live, mb.live_first, mb.live_n)) return RGB_E_INVAL;
+  }
+  const uint64_t need = select_pass(members, n_members, segrefs, live, nullptr, nullptr, false);
+  if (need > 0xFFFFFFFFull) return RGB_E_INVAL;
+  if (!sizing) {
+    if (need > live_out_cap || (n_segrefs && !picks) || (need && !live_out)) return RGB_E_INVAL;
+    (void)select_pass(members, n_members, segrefs, live, picks, live_out, true);
+  }
+  *n_live_out = (uint32_t)need;
+  return RGB_OK;
+}
+
+extern "C" int rgb_segment_compact_take_groups(rgb_seg_take_member *members, uint32_t n_members, const rgb_seg_info *infos,
+                                               const uint64_t *num_live, uint32_t n_sources, uint64_t max_count,
+                                               uint64_t max_size, uint32_t *group_of) {
+  if ((n_members && !members) || (n_sources && (!infos || !num_live || !group_of))) return RGB_E_INVAL;
+  uint64_t next = 0;
+  for (uint32_t m = 0; m < n_members; ++m) {
+    if (members[m].src_first > n_sources || members[m].src_n > n_sources - members[m].src_first) return RGB_E_INVAL;
+    if (members[m].src_first < next) return RGB_E_INVAL;
+    next = (uint64_t)members[m].src_first + members[m].src_n;
+  }
+  for (uint32_t s = 0; s < n_sources; ++s) group_of[s] = RGB_SEG_GROUP_NONE;   /* (a source no member names stays so) */
+  for (uint32_t m = 0; m < n_members; ++m) {
+    rgb_seg_take_member &mb = members[m];
+    uint32_t *of = group_of + mb.src_first;
+    uint32_t groups = 0, in_group = 0;                   /* in_group: the length of take_group's accumulator */
+    uint64_t cnt = max_count, size = max_size;           /* the budgets left */
+    bool crash = false;
+    uint32_t k = 0;
+    while (k < mb.src_n && !crash) {
+      const rgb_seg_info &in = infos[mb.src_first + k];
+      const uint64_t nl = num_live[mb.src_first + k];
+      /* NumLive / NumEnts < 0.5 orelse LiveSz / AllDataSz < 0.5, as integers: x / y < 0.5 iff 2 x < y for y > 0, which
+       * is what the float division answers while x and y are below 2^53 (both conversions and the quotient's
+       * comparison with 0.5 are then exact enough: 2 x and y are integers).  A negative AllDataSz (Sz < IdxSz) makes
+       * the quotient <= 0. */
+      bool compactable;
+      if (in.num_entries == 0u) { crash = true; break; }
+      if (nl < 0x8000000000000000ull && 2u * nl < (uint64_t)in.num_entries) {
+        compactable = true;
+      } else if (in.size == in.index_size) {
+        crash = true; break;
+      } else if (in.size < in.index_size) {
+        compactable = true;
+      } else {
+        const uint64_t all = in.size - in.index_size;
+        compactable = in.live_size < 0x8000000000000000ull && 2u * in.live_size < all;
+      }
+      if (compactable) {
+        if (nl > cnt || in.live_size > size) {           /* MaxCnt - NumLive < 0 orelse MaxSz - LiveSz < 0 */
+          if (in_group == 0u) { of[k++] = RGB_SEG_GROUP_NONE; continue; }
+          groups += 1u; in_group = 0u; cnt = max_count; size = max_size;      /* the source stays for the next group */
+          continue;
+        }
+        of[k++] = groups; in_group += 1u; cnt -= nl; size -= in.live_size;
+      } else {
+        of[k++] = RGB_SEG_GROUP_NONE;
+        if (in_group) { groups += 1u; in_group = 0u; cnt = max_count; size = max_size; }
+      }
+    }
+    if (in_group) groups += 1u;
+    if (crash) {
+      for (uint32_t j = 0; j < mb.src_n; ++j) of[j] = RGB_SEG_GROUP_NONE;
+      groups = 0u;
+    }
+    mb.n_groups = groups;
+    mb.status = crash ? RGB_SEG_TAKE_BADARITH : RGB_SEG_TAKE_OK;
+  }
+  return RGB_OK;
+}
+
+/* Library-internal (rgb_segment.hip calls it; not in the header): the descriptors of a batched compaction.  Per source
+ * asked[s] = its live indexes and group_of_src[s] = its group (0xFFFFFFFF: none), per pair rank[i] as
+ * rgb_seg_compact_check, per group max_counts[g]; *sum_bytes = the n_bytes of the sources that groups name
+ * (saturating), *total_count = the live indexes of all groups.  Every output may be NULL.  with_out: the groups' out
+ * ranges lie inside out_bytes and do not overlap (`order`: scratch of n_groups values for that, may be NULL without). */
+extern "C" int rgb_seg_compact_groups_check(const rgb_seg_group *groups, uint32_t n_groups, const rgb_seg_source *sources,
+                                            uint32_t n_sources, const uint64_t *live, uint32_t n_live, uint64_t files_bytes,
+                                            int with_out, uint64_t out_bytes, uint32_t *order, uint32_t *asked,
+                                            uint32_t *group_of_src, uint32_t *rank, uint32_t *max_counts,
+                                            uint64_t *sum_bytes, uint64_t *total_count) {
+  if ((n_groups && !groups) || (n_sources && !sources) || (n_live && !live)) return RGB_E_INVAL;
+  if (with_out && n_groups && !order) return RGB_E_INVAL;
+  if (group_of_src) for (uint32_t s = 0; s < n_sources; ++s) group_of_src[s] = 0xFFFFFFFFu;
+  if (asked) for (uint32_t s = 0; s < n_sources; ++s) asked[s] = 0u;
+  for (uint32_t s = 0; s < n_sources; ++s)               /* every source, named by a group or not: its header is read */
+    if (sources[s].offset > files_bytes || sources[s].n_bytes > files_bytes - sources[s].offset) return RGB_E_INVAL;
+  /* a pair's rank within its source is kept per pair: two named sources may share pairs only from the same first pair
+   * on.  owner[i] = the live_first of the slice that reached pair i first (n_live: none yet). */
+  struct owners {
+    uint32_t *p;
+    explicit owners(uint32_t n) : p(n ? new uint32_t[n] : nullptr) { for (uint32_t i = 0; i < n; ++i) p[i] = n; }
+    ~owners() { delete[] p; }
+  } owner(n_groups ? n_live : 0u);
+  uint64_t next = 0, sum = 0, total = 0;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    const rgb_seg_group &gr = groups[g];
+    if (gr.src_first > n_sources || gr.src_n > n_sources - gr.src_first) return RGB_E_INVAL;
+    if (gr.src_n && gr.src_first < next) return RGB_E_INVAL;                  /* ascending and disjoint */
+    if (gr.src_n) next = (uint64_t)gr.src_first + gr.src_n;
+    if (with_out && (gr.out_offset > out_bytes || gr.out_bytes > out_bytes - gr.out_offset)) return RGB_E_INVAL;
+    uint64_t in_group = 0;
+    for (uint32_t q = 0; q < gr.src_n; ++q) {
+      const uint32_t s = gr.src_first + q;
+      const rgb_seg_source &src = sources[s];
+      sum = sum + src.n_bytes < sum ? ~0ull : sum + src.n_bytes;
+      if (src.live_first > n_live || src.live_n > n_live - src.live_first) return RGB_E_INVAL;
+      if (!pairs_ok(live, src.live_first, src.live_n)) return RGB_E_INVAL;
+      uint64_t in_source = 0;
+      for (uint32_t k = 0; k < src.live_n; ++k) {
+        const uint64_t i = (uint64_t)src.live_first + k;
+        const uint64_t count = live[2 * i + 1] - live[2 * i];                 /* + 1, below */
+        if (count >= 65535u || in_source + count + 1u > 65535u) return RGB_E_INVAL;
+        if (owner.p[i] != n_live && owner.p[i] != src.live_first) return RGB_E_INVAL;
+        owner.p[i] = src.live_first;
+        if (rank) rank[i] = (uint32_t)in_source;
+        in_source += count + 1u;
+      }
+      in_group += in_source;
+      if (in_group > 65535u) return RGB_E_INVAL;
+      if (asked) asked[s] = (uint32_t)in_source;
+      if (group_of_src) group_of_src[s] = g;
+    }
+    if (max_counts) max_counts[g] = (uint32_t)in_group;
+    total += in_group;
+  }
+  if (total > 0xFFFFFFFFull - 256u) return RGB_E_INVAL;
+  if (with_out && n_groups) {
+    /* no two non-empty out ranges meet: sorted by offset (a heap sort on the indexes: no allocation here) */
+    const uint32_t n = n_groups;
+    for (uint32_t g = 0; g < n; ++g) order[g] = g;
+    auto less = [&](uint32_t a, uint32_t b) { return groups[a].out_offset < groups[b].out_offset; };
+    auto sift = [&](uint32_t root, uint32_t end) {
+      for (;;) {
+        uint32_t child = 2u * root + 1u;
+        if (child >= end) return;
+        if (child + 1u < end && less(order[child], order[child + 1u])) child += 1u;
+        if (!less(order[root], order[child])) return;
+        const uint32_t t = order[root]; order[root] = order[child]; order[child] = t;
+        root = child;
+      }
+    };
+    for (uint32_t i = n / 2u; i-- > 0u;) sift(i, n);
+    for (uint32_t end = n; end-- > 1u;) {
+      const uint32_t t = order[0]; order[0] = order[end]; order[end] = t;
+      sift(0u, end);
+    }
+    uint64_t behind = 0;                                 /* the end of the non-empty ranges so far */
+    for (uint32_t k = 0; k < n; ++k) {
+      const rgb_seg_group &gr = groups[order[k]];
+      if (gr.out_bytes == 0u) continue;
+      if (gr.out_offset < behind) return RGB_E_INVAL;
+      behind = gr.out_offset + gr.out_bytes;
+    }
+  }
+  if (sum_bytes) *sum_bytes = sum;
+  if (total_count) *total_count = total;
+  return RGB_OK;
+}
+
+extern "C" int rgb_segment_compact_groups_bound(rgb_seg_group *groups, uint32_t n_groups, const rgb_seg_source *sources,
+                                                uint32_t n_sources, const uint64_t *live, uint32_t n_live,
+                                                uint64_t files_bytes, uint64_t *total_out, uint32_t *max_counts) {
+  if (!total_out) return RGB_E_INVAL;
+  int rc = rgb_seg_compact_groups_check(groups, n_groups, sources, n_sources, live, n_live, files_bytes, 0, 0, nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  /* (the counts once more, so that nothing is written before every group has been accepted) */
+  uint64_t pos = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    pos = 0;
+    for (uint32_t g = 0; g < n_groups; ++g) {
+      uint64_t count = 0, bytes = 0;
+      for (uint32_t q = 0; q < groups[g].src_n; ++q) {
+        const rgb_seg_source &src = sources[groups[g].src_first + q];
+        for (uint32_t k = 0; k < src.live_n; ++k) {
+          const uint64_t i = (uint64_t)src.live_first + k;
+          count += live[2 * i + 1] - live[2 * i] + 1u;
+        }
+        if (bytes + src.n_bytes < bytes) return RGB_E_INVAL;
+        bytes += src.n_bytes;
+      }
+      const uint64_t head = (uint64_t)RGB_SEG_HEADER_BYTES + (uint64_t)RGB_SEG_RECORD_BYTES * count;
+      if (bytes + head < bytes || pos + (bytes + head) < pos) return RGB_E_INVAL;
+      if (pass) {
+        groups[g].out_offset = pos; groups[g].out_bytes = bytes + head;
+        if (max_counts) max_counts[g] = (uint32_t)count;
+      }
+      pos += bytes + head;
+    }
+  }
+  *total_out = pos;
   return RGB_OK;
 }
 

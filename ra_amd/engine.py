@@ -48,7 +48,9 @@ WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "r
                "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
                "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate",
                "rgb_segment_compact_bound", "rgb_segment_info_device", "rgb_segment_info", "rgb_segment_compact_device",
-               "rgb_segment_compact", "rgb_segment_flush_bound", "rgb_segment_flush_device", "rgb_segment_flush",
+               "rgb_segment_compact", "rgb_segment_compact_select", "rgb_segment_compact_take_groups",
+               "rgb_segment_compact_groups_bound", "rgb_segment_compact_groups_device", "rgb_segment_compact_groups",
+               "rgb_segment_flush_bound", "rgb_segment_flush_device", "rgb_segment_flush",
                "rgb_segment_read_device", "rgb_segment_read",
                "rgb_crc32_spans_device", "rgb_crc32_spans", "rgb_snapshot_layout", "rgb_snapshot_build_device",
                "rgb_snapshot_build", "rgb_snapshot_validate_device", "rgb_snapshot_validate"]                                                                                 # include/ra_gpu_wal.h
@@ -217,6 +219,13 @@ def lib():
     L.rgb_segment_info.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, vp]
     L.rgb_segment_compact_device.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp, C.c_uint64, vp, vp]
     L.rgb_segment_compact.argtypes = [vp, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp, C.c_uint64, vp]
+    L.rgb_segment_compact_select.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, u32, u32p]
+    L.rgb_segment_compact_take_groups.argtypes = [vp, u32, vp, vp, u32, C.c_uint64, C.c_uint64, vp]
+    L.rgb_segment_compact_groups_bound.argtypes = [vp, u32, vp, u32, vp, u32, C.c_uint64, u64p, vp]
+    L.rgb_segment_compact_groups_device.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp,
+                                                    C.c_uint64, vp, vp]
+    L.rgb_segment_compact_groups.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp,
+                                             C.c_uint64, vp]
     L.rgb_segment_flush_bound.argtypes = [vp, u32, u32, C.c_uint64, u64p, u32p]
     L.rgb_segment_flush_device.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp,
                                            C.c_uint64, vp, vp]
@@ -716,6 +725,106 @@ class RaGpuBatch:
         ok = int(res["status"][0]) == abi.SEG_COMPACT_OK
         return res[0], (out[:int(res["file_bytes"][0])] if ok else None)
 
+    # -- major compaction for many members: any number of groups in one call (include/ra_gpu_wal.h) --
+    def segment_compact_groups_device(self, groups: np.ndarray, sources: np.ndarray, d_files: int, files_bytes: int, live,
+                                      d_out: int, out_bytes: int, d_results: int, max_size: int = abi.SEG_MAX_SIZE_B,
+                                      flags: int = 0, stream: int = 0):
+        """Every group's image at d_out + out_offset and one abi.SEG_COMPACT_RESULT_DTYPE row per group into d_results:
+        per group exactly what segment_compact_device gives for it alone.  `groups` (abi.SEG_GROUP_DTYPE), `sources` and
+        `live` are host arrays; enqueues and returns."""
+        groups = np.ascontiguousarray(groups, dtype=abi.SEG_GROUP_DTYPE)
+        sources, live, n_live = _compact_args(sources, live)
+        self._check(self._L.rgb_segment_compact_groups_device(
+            self._h, groups.ctypes.data if len(groups) else None, len(groups),
+            sources.ctypes.data if len(sources) else None, len(sources), d_files or None, files_bytes,
+            live.ctypes.data if live is not None else None, n_live, max_size, flags, d_out or None, out_bytes,
+            d_results or None, stream or None), "rgb_segment_compact_groups_device")
+
+    def segment_compact_groups(self, groups: np.ndarray, sources: np.ndarray, files: np.ndarray, live,
+                               max_size: int = abi.SEG_MAX_SIZE_B, flags: int = 0, out: np.ndarray | None = None):
+        """Host-buffer form: (result rows, images).  images[g] is a view of `out` when the group's status is
+        abi.SEG_COMPACT_OK and None otherwise; `out` (uint8) defaults to a buffer that ends with the last group's range,
+        and only the good images' own bytes are written."""
+        groups = np.ascontiguousarray(groups, dtype=abi.SEG_GROUP_DTYPE)
+        sources, live, n_live = _compact_args(sources, live)
+        files = np.ascontiguousarray(files, dtype=np.uint8)
+        if out is None:
+            out = np.zeros(max([int(g["out_offset"]) + int(g["out_bytes"]) for g in groups], default=0), dtype=np.uint8)
+        res = np.zeros(len(groups), dtype=abi.SEG_COMPACT_RESULT_DTYPE)
+        self._check(self._L.rgb_segment_compact_groups(
+            self._h, groups.ctypes.data if len(groups) else None, len(groups),
+            sources.ctypes.data if len(sources) else None, len(sources), files.ctypes.data if len(files) else None,
+            len(files), live.ctypes.data if live is not None else None, n_live, max_size, flags,
+            out.ctypes.data if len(out) else None, len(out), res.ctypes.data if len(groups) else None),
+            "rgb_segment_compact_groups")
+        images = [out[int(g["out_offset"]):int(g["out_offset"]) + int(r["file_bytes"])]
+                  if int(r["status"]) == abi.SEG_COMPACT_OK else None for g, r in zip(groups, res)]
+        return res, images
+
+    def major_compaction_plan(self, members, files: np.ndarray, max_count: int = abi.SEG_MAX_ENTRIES,
+                              max_size: int = abi.SEG_MAX_SIZE_B) -> dict:
+        """The plan of ra_log_segments:major_compaction/3 (src/ra_log_segments.erl:741-835) for many members: select,
+        then info/2 of every file that holds live indexes (in chunks of at most abi.SEG_COMPACT_MAX_SOURCES sources),
+        then the groups.  `members`: per member (segrefs, live) -- segrefs a list of (offset, n_bytes, (range_first,
+        range_last)) of the member's files inside `files`, newest first as compactable_segrefs/2 gives them; live the
+        member's live pairs.  -> dict: `groups` (abi.SEG_GROUP_DTYPE, laid out back to back by
+        segment_compact_groups_bound), `sources` (abi.SEG_SOURCE_DTYPE, the groups' sources oldest first), `live`
+        (pairs), `out_bytes`, `max_counts`, and per member `group_files` (per group of `groups`, in order: (member,
+        the file ordinals in the member's segref list)), `unreferenced` (file ordinals, the Delete list in the fold's
+        order), `skipped` (compactable candidates that joined no group) and `status` (abi.SEG_TAKE_*); for callers
+        that want to look further, `candidates` ((member, file ordinal, segref number) of every file with live indexes,
+        oldest first per member) and their `infos` rows.
+        info/2 goes through the host-buffer segment_info, which stages `files` once per chunk and answers a file
+        with a damaged header with RgbError(RGB_E_INVAL) for the whole call -- as the reference's info/2 crashes the
+        compaction that meets it: ONE such file among the candidates fails the plan of every member of the call,
+        unlike the copy, where it fails its own group only.  A caller that must survive it plans such members apart."""
+        files = np.ascontiguousarray(files, dtype=np.uint8)
+        mem = np.zeros(len(members), dtype=abi.SEG_MEMBER_DTYPE)
+        segrefs, live = [], []
+        for m, (refs, pairs) in enumerate(members):
+            pairs = np.asarray(pairs if pairs is not None else [], dtype=np.uint64).reshape(-1, 2)
+            mem[m] = (len(segrefs), len(refs), len(live), len(pairs))
+            segrefs += [(r[2][0], r[2][1]) for r in refs]
+            live += [tuple(p) for p in pairs.tolist()]
+        picks, live_out = segment_compact_select(mem, segrefs, live)
+        # the candidates of every member, OLDEST first (the fold prepends): info/2 with the selection as the live list
+        cand = np.zeros(len(picks), dtype=abi.SEG_SOURCE_DTYPE)
+        where, take = [], np.zeros(len(members), dtype=abi.SEG_TAKE_MEMBER_DTYPE)
+        unreferenced = [[] for _ in members]
+        for m, (refs, _) in enumerate(members):
+            first = len(where)
+            base = int(mem["segref_first"][m])
+            for k in range(len(refs)):
+                if int(picks["flags"][base + k]) & abi.SEG_PICK_UNREFERENCED:
+                    unreferenced[m].insert(0, k)                      # [Fn0 | Del]
+            for k in reversed(range(len(refs))):
+                if not int(picks["flags"][base + k]) & abi.SEG_PICK_UNREFERENCED:
+                    cand[len(where)] = (refs[k][0], refs[k][1], picks["live_first"][base + k], picks["live_n"][base + k], 0)
+                    where.append((m, k, base + k))
+            take[m] = (first, len(where) - first, 0, 0)
+        cand = cand[:len(where)]
+        infos = np.zeros(len(cand), dtype=abi.SEG_INFO_DTYPE)
+        for lo in range(0, len(cand), abi.SEG_COMPACT_MAX_SOURCES):
+            hi = min(len(cand), lo + abi.SEG_COMPACT_MAX_SOURCES)
+            infos[lo:hi] = self.segment_info(cand[lo:hi], files, live_out)
+        num_live = np.array([int(picks["num_live"][w[2]]) for w in where], dtype=np.uint64)
+        take, group_of = segment_compact_take_groups(take, infos, num_live, max_count, max_size)
+        rows, sources, group_files, skipped = [], [], [], [[] for _ in members]
+        for m in range(len(members)):
+            first, n = int(take["src_first"][m]), int(take["src_n"][m])
+            for g in range(int(take["n_groups"][m])):
+                idx = [first + j for j in range(n) if int(group_of[first + j]) == g]
+                rows.append((len(sources), len(idx), 0, 0))
+                sources += idx
+                group_files.append((m, [where[i][1] for i in idx]))
+            skipped[m] = [where[first + j][1] for j in range(n) if int(group_of[first + j]) == abi.SEG_GROUP_NONE]
+        groups = np.array(rows, dtype=abi.SEG_GROUP_DTYPE).reshape(-1)
+        sources = cand[np.array(sources, dtype=np.int64)]
+        groups, out_bytes, max_counts = segment_compact_groups_bound(groups, sources, live_out, len(files))
+        return dict(groups=groups, sources=sources, live=live_out, out_bytes=out_bytes, max_counts=max_counts,
+                    group_files=group_files, unreferenced=unreferenced, skipped=skipped,
+                    status=[int(x) for x in take["status"]], infos=infos, candidates=where)
+
     # -- mem-table flush: the entries of many writers into their segment files (include/ra_gpu_wal.h) --
     def segment_flush_device(self, writers: np.ndarray, d_entries: int, n_entries: int, d_data: int, data_bytes: int,
                              d_pieces: int, pieces_cap: int, d_out: int, out_bytes: int, d_result: int,
@@ -1053,6 +1162,67 @@ def segment_compact_bound(sources, live, files_bytes: int):
     if rc != 0:
         raise RgbError(rc, "rgb_segment_compact_bound")
     return int(bound.value), int(max_count.value)
+
+
+def segment_compact_select(members, segrefs, live, sizing: bool = False):
+    """The fold of major_compaction/3 and minor_compaction/2 for many members (host helper, no device work): `members`
+    as abi.SEG_MEMBER_DTYPE, `segrefs` (range_first, range_last) pairs newest first, `live` pairs.  -> (one
+    abi.SEG_PICK_DTYPE row per segref, the selected pairs as an (n, 2) uint64 array); sizing: the number of pairs."""
+    members = np.ascontiguousarray(members, dtype=abi.SEG_MEMBER_DTYPE)
+    segrefs = np.ascontiguousarray(segrefs, dtype=np.uint64).reshape(-1)
+    live = np.ascontiguousarray(live if live is not None else [], dtype=np.uint64).reshape(-1)
+    if len(segrefs) % 2 or len(live) % 2:
+        raise ValueError("segrefs and the live list are (first, last) pairs")
+    n_out = C.c_uint32(0)
+    args = (members.ctypes.data if len(members) else None, len(members), segrefs.ctypes.data if len(segrefs) else None,
+            len(segrefs) // 2, live.ctypes.data if len(live) else None, len(live) // 2)
+    rc = lib().rgb_segment_compact_select(*args, None, None, 0, C.byref(n_out))
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_compact_select")
+    if sizing:
+        return int(n_out.value)
+    picks = np.zeros(len(segrefs) // 2, dtype=abi.SEG_PICK_DTYPE)
+    out = np.zeros((max(1, n_out.value), 2), dtype=np.uint64)
+    rc = lib().rgb_segment_compact_select(*args, picks.ctypes.data, out.ctypes.data, n_out.value, C.byref(n_out))
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_compact_select")
+    return picks, out[:n_out.value]
+
+
+def segment_compact_take_groups(members, infos, num_live, max_count: int = abi.SEG_MAX_ENTRIES,
+                                max_size: int = abi.SEG_MAX_SIZE_B):
+    """compaction_groups/3 with take_group/3 per member (host helper): `members` as abi.SEG_TAKE_MEMBER_DTYPE (src_first,
+    src_n), `infos` (abi.SEG_INFO_DTYPE) and `num_live` per source, oldest first.  -> (members with n_groups and status
+    filled in, the group ordinal of every source or abi.SEG_GROUP_NONE)."""
+    members = np.ascontiguousarray(members, dtype=abi.SEG_TAKE_MEMBER_DTYPE).copy()
+    infos = np.ascontiguousarray(infos, dtype=abi.SEG_INFO_DTYPE)
+    num_live = np.ascontiguousarray(num_live, dtype=np.uint64)
+    if len(num_live) != len(infos):
+        raise ValueError("one num_live per info row")
+    group_of = np.full(max(1, len(infos)), abi.SEG_GROUP_NONE, dtype=np.uint32)
+    rc = lib().rgb_segment_compact_take_groups(members.ctypes.data if len(members) else None, len(members),
+                                               infos.ctypes.data if len(infos) else None,
+                                               num_live.ctypes.data if len(infos) else None, len(infos), max_count,
+                                               max_size, group_of.ctypes.data)
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_compact_take_groups")
+    return members, group_of[:len(infos)]
+
+
+def segment_compact_groups_bound(groups, sources, live, files_bytes: int):
+    """(a copy of `groups` with out_offset / out_bytes laid out back to back, the bytes of `out` in all, MaxCount per
+    group) -- host helper, no device work; RgbError(RGB_E_INVAL) for what the batched compact calls refuse."""
+    groups = np.ascontiguousarray(groups, dtype=abi.SEG_GROUP_DTYPE).copy()
+    sources, live, n_live = _compact_args(sources, live)
+    total = C.c_uint64(0)
+    counts = np.zeros(max(1, len(groups)), dtype=np.uint32)
+    rc = lib().rgb_segment_compact_groups_bound(groups.ctypes.data if len(groups) else None, len(groups),
+                                                sources.ctypes.data if len(sources) else None, len(sources),
+                                                live.ctypes.data if live is not None else None, n_live, files_bytes,
+                                                C.byref(total), counts.ctypes.data)
+    if rc != 0:
+        raise RgbError(rc, "rgb_segment_compact_groups_bound")
+    return groups, int(total.value), counts[:len(groups)]
 
 
 def segment_flush_bound(writers, n_entries: int, data_bytes: int):
