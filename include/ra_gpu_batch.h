@@ -31,6 +31,10 @@ extern "C" {
 #endif
 
 #define RGB_ABI_VERSION   10u
+/* What a library of RGB_ABI_VERSION adds without changing a call.  1: device-resident decision streams hold the five
+ * compact forms below, which only THIS header's rgb_decision_expand reads -- a consumer compiled with the decoder of
+ * minor 0 misreads them, and no call reports the minor: rebuild the consumers of such streams with the library. */
+#define RGB_ABI_MINOR     1u
 #define RGB_UNDEF         UINT64_MAX   /* Erlang 'undefined' (index or term)            */
 #define RGB_NONE          0xFFu        /* undefined ra_server_id() (member slot)        */
 #define RGB_MAX_MEMBERS   8u           /* members per Raft group held on the device     */
@@ -279,18 +283,32 @@ typedef struct rgb_decision {
  *   bytes 8..11  flags with RGB_F_COMPACT        bytes 12..15  aux (where invariant / heartbeat_to / cancel_backoff sit;
  *                                                              all three are 0 in every decision that is compacted)
  *   bytes 16..23 A    bytes 24..31 B
- * Three forms, told apart by kind and flags (every other field of the expanded record is 0):
- *   counted     kind AER_REPLY, or WRITTEN without RGB_F_REPLY: commit_index = A, last_applied = B
+ * Five forms, told apart by kind and flags (every other field of the expanded record is 0):
+ *   counted     no reply, no write: commit_index = A, last_applied = B, reply_next_index = aux.  With none but plain
+ *               flags (below): kind AER_REPLY, WRITTEN, AER, VOTE_RESULT, APPEND, PRE_VOTE_RESULT, SNAPSHOT_WRITTEN,
+ *               HEARTBEAT_RPC, aux = 0; kind VOTE_RESULT with exactly RGB_F_BECAME_LEADER | RGB_F_ROLE_CHANGED |
+ *               RGB_F_LEADER_CHANGED, aux = 0; kind HEARTBEAT_REPLY with exactly RGB_F_QUERY_QUORUM, aux = the consensus
+ *               query index (below 2^32)
  *   wrote       kind AER with RGB_F_WROTE (no reply): reply_last_index = A, reply_next_index = A - aux[0:16],
  *               commit_index = B, last_applied = A - aux[16:32]
  *   confirmed   kind AER or WRITTEN with RGB_F_REPLY | RGB_F_REPLY_SUCCESS: reply_next_index = A + 1, reply_term = B,
  *               reply_last_index = A - aux[0:8], reply_last_term = B - aux[8:12],
  *               commit_index = A + aux[12:22] - 512, last_applied = A + 1 - aux[22:32]
- * Beside the flags that name its form a compacted decision carries only flags that come with no words of their own:
- * RGB_F_LEADER_MSG, RGB_F_APPLIED, RGB_F_AUX_EVAL, RGB_F_PIPELINE.  Every difference above is taken in the integers: a
- * negative one (reply_last_index above A, last_applied above A + 1, ..) does not fit, nor does reply_next_index = 0.
+ *   answered    kind HEARTBEAT_RPC with RGB_F_REPLY | RGB_F_REPLY_HEARTBEAT: commit_index = A, reply_term = B,
+ *               reply_next_index = aux[0:16], last_applied = A + 32768 - aux[16:32]
+ *   stood       kind PRE_VOTE_RESULT with RGB_F_SEND_VOTE_REQUESTS (no reply): reply_last_index = A, reply_term = B,
+ *               reply_last_term = B - aux[0:8], commit_index = A - aux[8:20], last_applied = A - aux[20:32]
+ * Beside the flags that name its form a compacted decision carries only flags that come with no words of their own.
+ * The plain ones, in every form: RGB_F_LEADER_MSG, RGB_F_APPLIED, RGB_F_AUX_EVAL, RGB_F_PIPELINE.  The flags of a
+ * change -- RGB_F_PERSIST, RGB_F_LEADER_CHANGED, RGB_F_REPROCESSED, RGB_F_ROLE_CHANGED -- in answered and stood, and in
+ * the forms of kind AER (wrote, confirmed) when RGB_F_ROLE_CHANGED or RGB_F_LEADER_CHANGED is among them (an
+ * append_entries_rpc that only stored a term is written in full).  Every difference above is taken in the integers:
+ * one outside its field (reply_last_index above A, last_applied above A + 1, ..) does not fit, nor does
+ * reply_next_index = 0 in confirmed.
  * A decision whose values do not fit (or that is of any other shape) is written in full, without the flag: the
- * encoding loses nothing.  The kernels compact at the store; rgb_decision_expand is the only decoder a consumer needs. */
+ * encoding loses nothing.  The kernels compact at the store; rgb_decision_expand is the only decoder a consumer needs.
+ * (RGB_ABI_MINOR 0 wrote counted for AER_REPLY and WRITTEN only, wrote and confirmed without the flags of a change, and
+ * none of the other forms: this decoder reads those streams as well.) */
 static inline void rgb_decision_expand(rgb_decision *d) {
   if (!(d->flags & RGB_F_COMPACT)) return;
   uint64_t w[4];
@@ -305,15 +323,21 @@ static inline void rgb_decision_expand(rgb_decision *d) {
   d->flags &= ~RGB_F_COMPACT;
   d->invariant = 0; d->heartbeat_to = 0; d->cancel_backoff = 0;
   d->reply_term = d->reply_next_index = d->reply_last_index = d->reply_last_term = 0;
-  if (d->flags & RGB_F_REPLY) {
+  if (d->flags & RGB_F_REPLY_HEARTBEAT) {                                           /* answered */
+    d->commit_index = A; d->reply_term = B;
+    d->reply_next_index = aux & 0xFFFFu; d->last_applied = A + 32768u - (aux >> 16);
+  } else if (d->flags & RGB_F_REPLY) {                                              /* confirmed */
     d->reply_next_index = A + 1; d->reply_term = B;
     d->reply_last_index = A - (aux & 0xFFu); d->reply_last_term = B - ((aux >> 8) & 0xFu);
     d->commit_index = A + ((aux >> 12) & 0x3FFu) - 512u; d->last_applied = A + 1 - ((aux >> 22) & 0x3FFu);
   } else if (d->flags & RGB_F_WROTE) {
     d->reply_last_index = A; d->reply_next_index = A - (aux & 0xFFFFu);
     d->commit_index = B; d->last_applied = A - (aux >> 16);
-  } else {
-    d->commit_index = A; d->last_applied = B;
+  } else if (d->flags & RGB_F_SEND_VOTE_REQUESTS) {                                 /* stood */
+    d->reply_last_index = A; d->reply_term = B; d->reply_last_term = B - (aux & 0xFFu);
+    d->commit_index = A - ((aux >> 8) & 0xFFFu); d->last_applied = A - (aux >> 20);
+  } else {                                                                          /* counted */
+    d->commit_index = A; d->last_applied = B; d->reply_next_index = aux;
   }
 }
 

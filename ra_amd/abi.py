@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 ABI_VERSION = 10
+ABI_MINOR = 1                  # RGB_ABI_MINOR: 1 = the compact decision forms expand_decisions reads (a superset of minor 0's)
 CFG_ROUNDS_PER_LAUNCH = 1      # rgb_config.flags: rgb_submit launches one kernel per sub-tick round (the default since round 5)
 CFG_SUBMIT_TRAINS = 16         # rgb_config.flags: opt-in -- rgb_submit fuses the sub-tick rounds of a batch into one train launch
 CFG_FUSE_PIPELINE = 4          # rgb_config.flags: a leader's success reply / written event carries its pipeline_rpcs event's rpcs (opt-in)
@@ -312,6 +313,52 @@ def log_entries(st_row) -> list:
     return out
 
 
+F_COMPACT_PLAIN = F_LEADER_MSG | F_APPLIED | F_AUX_EVAL | F_PIPELINE      # flags that carry no words of their own
+F_COMPACT_CHANGE = F_PERSIST | F_LEADER_CHANGED | F_REPROCESSED | F_ROLE_CHANGED     # .. nor do the flags of a change
+COMPACT_FORM_NAMES = ("full", "counted", "wrote", "confirmed", "answered", "stood")
+_COUNTED_KINDS = (MSG_AER_REPLY, MSG_WRITTEN, MSG_AER, MSG_VOTE_RESULT, MSG_APPEND, MSG_PRE_VOTE_RESULT,
+                  MSG_SNAPSHOT_WRITTEN, MSG_HEARTBEAT_RPC)
+
+
+def compact_forms(dec: np.ndarray) -> np.ndarray:
+    """Which compact form (index into COMPACT_FORM_NAMES, 0 = none) the encoder of include/ra_gpu_batch.h gives each
+    FULL record of `dec`: the classification of compact_decision (rgb_kernels.hip) on the host, for counting and tests."""
+    d = np.asarray(dec, dtype=DECISION_DTYPE)
+    u = np.uint64
+    kind, flags = d["kind"], d["flags"]
+    shape = flags & ~np.uint32(F_COMPACT_PLAIN)
+    stem = shape & ~np.uint32(F_COMPACT_CHANGE)
+    term, nxt, last, lterm, ci, la = (d[f] for f in ("reply_term", "reply_next_index", "reply_last_index",
+                                                    "reply_last_term", "commit_index", "last_applied"))
+    ok = (d["invariant"] == 0) & (d["heartbeat_to"] == 0) & (d["cancel_backoff"] == 0) & ((flags & F_COMPACT) == 0)
+    form = np.zeros(len(d), dtype=np.uint8)
+    with np.errstate(over="ignore"):
+        def within(hi, lo, limit):          # 0 <= hi - lo <= limit in the integers
+            return (hi >= lo) & (hi - lo <= u(limit))
+
+        def biased(hi, lo, bias, limit):    # 0 <= hi + bias - lo <= limit in the integers
+            up = hi >= lo
+            return np.where(up, hi - lo, lo - hi) <= np.where(up, u(limit - bias), u(bias))
+
+        aer = (kind == MSG_AER) & ((stem == shape) | ((shape & (F_ROLE_CHANGED | F_LEADER_CHANGED)) != 0))
+        counted = (((shape == 0) & np.isin(kind, _COUNTED_KINDS)) |
+                   ((kind == MSG_VOTE_RESULT) & (shape == (F_BECAME_LEADER | F_ROLE_CHANGED | F_LEADER_CHANGED)))) & \
+            ((term | nxt | last | lterm) == 0)
+        counted |= (kind == MSG_HEARTBEAT_REPLY) & (shape == F_QUERY_QUORUM) & ((term | last | lterm) == 0) & \
+            (nxt <= u(0xFFFFFFFF))
+        wrote = (stem == F_WROTE) & aer & ((term | lterm) == 0) & within(last, nxt, 0xFFFF) & within(last, la, 0xFFFF)
+        A = nxt - u(1)
+        confirmed = (stem == (F_REPLY | F_REPLY_SUCCESS)) & (aer | ((kind == MSG_WRITTEN) & (stem == shape))) & (nxt != 0) & \
+            within(A, last, 0xFF) & within(term, lterm, 0xF) & biased(ci, A, 512, 0x3FF) & within(nxt, la, 0x3FF)
+        answered = (kind == MSG_HEARTBEAT_RPC) & (stem == (F_REPLY | F_REPLY_HEARTBEAT)) & ((last | lterm) == 0) & \
+            (nxt <= u(0xFFFF)) & biased(ci, la, 0x8000, 0xFFFF)
+        stood = (kind == MSG_PRE_VOTE_RESULT) & (stem == F_SEND_VOTE_REQUESTS) & (nxt == 0) & within(term, lterm, 0xFF) & \
+            within(last, ci, 0xFFF) & within(last, la, 0xFFF)
+    for k, m in enumerate((counted, wrote, confirmed, answered, stood), 1):
+        form[ok & m] = k
+    return form
+
+
 def expand_decisions(dec: np.ndarray) -> np.ndarray:
     """rgb_decision_expand (include/ra_gpu_batch.h) over an array read from a DEVICE-RESIDENT decision stream: records
     with F_COMPACT were written as 32 bytes; the full records come back (a copy), the flag cleared."""
@@ -323,9 +370,18 @@ def expand_decisions(dec: np.ndarray) -> np.ndarray:
     aux = (w[:, 1] >> np.uint64(32)).astype(np.uint64)
     A, B = w[:, 2].copy(), w[:, 3].copy()
     flags = d["flags"] & ~np.uint32(F_COMPACT)
-    reply = c & ((flags & F_REPLY) != 0)
-    wrote = c & ~reply & ((flags & F_WROTE) != 0)
-    counted = c & ~reply & ~wrote
+    rest = c.copy()
+
+    def take(mask):
+        m = rest & mask
+        rest[m] = False
+        return m
+
+    answered = take((flags & F_REPLY_HEARTBEAT) != 0)
+    confirmed = take((flags & F_REPLY) != 0)
+    wrote = take((flags & F_WROTE) != 0)
+    stood = take((flags & F_SEND_VOTE_REQUESTS) != 0)
+    counted = rest
     with np.errstate(over="ignore"):
         d["flags"] = flags
         for f in ("invariant", "heartbeat_to", "cancel_backoff"):
@@ -333,16 +389,19 @@ def expand_decisions(dec: np.ndarray) -> np.ndarray:
         for f in ("reply_term", "reply_next_index", "reply_last_index", "reply_last_term"):
             d[f][c] = 0
         u = np.uint64
-        d["reply_next_index"][reply] = (A + u(1))[reply]
-        d["reply_term"][reply] = B[reply]
-        d["reply_last_index"][reply] = (A - (aux & u(0xFF)))[reply]
-        d["reply_last_term"][reply] = (B - ((aux >> u(8)) & u(0xF)))[reply]
-        d["commit_index"][reply] = (A + ((aux >> u(12)) & u(0x3FF)) - u(512))[reply]
-        d["last_applied"][reply] = (A + u(1) - ((aux >> u(22)) & u(0x3FF)))[reply]
-        d["reply_last_index"][wrote] = A[wrote]
-        d["reply_next_index"][wrote] = (A - (aux & u(0xFFFF)))[wrote]
-        d["commit_index"][wrote] = B[wrote]
-        d["last_applied"][wrote] = (A - (aux >> u(16)))[wrote]
-        d["commit_index"][counted] = A[counted]
-        d["last_applied"][counted] = B[counted]
+
+        def put(m, **fields):
+            for f, v in fields.items():
+                d[f][m] = v[m]
+
+        put(answered, commit_index=A, reply_term=B, reply_next_index=aux & u(0xFFFF),
+            last_applied=A + u(32768) - (aux >> u(16)))
+        put(confirmed, reply_next_index=A + u(1), reply_term=B, reply_last_index=A - (aux & u(0xFF)),
+            reply_last_term=B - ((aux >> u(8)) & u(0xF)), commit_index=A + ((aux >> u(12)) & u(0x3FF)) - u(512),
+            last_applied=A + u(1) - ((aux >> u(22)) & u(0x3FF)))
+        put(wrote, reply_last_index=A, reply_next_index=A - (aux & u(0xFFFF)), commit_index=B,
+            last_applied=A - (aux >> u(16)))
+        put(stood, reply_last_index=A, reply_term=B, reply_last_term=B - (aux & u(0xFF)),
+            commit_index=A - ((aux >> u(8)) & u(0xFFF)), last_applied=A - (aux >> u(20)))
+        put(counted, commit_index=A, last_applied=B, reply_next_index=aux)
     return d

@@ -2107,32 +2107,65 @@ __device__ __forceinline__ void make_decision(Dec &d, u32 server, unsigned role,
   d.w[2] = w2; d.w[3] = w3; d.w[4] = w4; d.w[5] = w5; d.w[6] = ci; d.w[7] = la;
 }
 
+/* hi + bias - lo, taken in the integers, where it lies in 0..limit (bias <= limit) */
+__device__ __forceinline__ bool biased_delta(u64 hi, u64 lo, u32 bias, u32 limit, u32 &out) {
+  const bool up = hi >= lo;
+  const u64 x = up ? hi - lo : lo - hi;
+  if (x > (u64)(up ? limit - bias : bias)) return false;
+  out = up ? bias + (u32)x : bias - (u32)x;
+  return true;
+}
+
 /* The compact form of a decision (include/ra_gpu_batch.h, "Compact decisions"): applied where a decision is staged for
- * its store, whatever path computed it; returns whether the record became 32 bytes.  Three shapes, each tested value
- * by value -- what does not fit stays a full record. */
+ * its store, whatever path computed it; returns whether the record became 32 bytes.  The header's five forms (counted with and without a
+ * query index), told apart by kind and flags, each tested value by value -- what does not fit stays a full record. */
 __device__ __forceinline__ bool compact_decision(Dec &d) {
   const u32 flags = (u32)d.w[1];
   const unsigned kind = (unsigned)(d.w[0] >> 56);
   if ((d.w[1] >> 32) != 0ull || (flags & RGB_F_COMPACT)) return false;             /* invariant / masks in use */
   const u32 plain = RGB_F_LEADER_MSG | RGB_F_APPLIED | RGB_F_AUX_EVAL | RGB_F_PIPELINE;     /* flags that carry no words */
+  /* .. and the flags of a change, which carry none either: part of a shape where the header's table says so */
+  const u32 change = RGB_F_PERSIST | RGB_F_LEADER_CHANGED | RGB_F_REPROCESSED | RGB_F_ROLE_CHANGED;
+  const u32 shape = flags & ~plain, stem = shape & ~change;
+  /* an append_entries_rpc's forms take the flags of a change only with a new role or a new leader among them */
+  const bool aer = kind == RGB_MSG_AER && (stem == shape || (shape & (RGB_F_ROLE_CHANGED | RGB_F_LEADER_CHANGED)) != 0u);
+  const u32 counted_kinds = (1u << RGB_MSG_AER_REPLY) | (1u << RGB_MSG_WRITTEN) | (1u << RGB_MSG_AER) | (1u << RGB_MSG_VOTE_RESULT) |
+                            (1u << RGB_MSG_APPEND) | (1u << RGB_MSG_PRE_VOTE_RESULT) | (1u << RGB_MSG_SNAPSHOT_WRITTEN) |
+                            (1u << RGB_MSG_HEARTBEAT_RPC);
+  const u64 term = d.w[2], next = d.w[3], last = d.w[4], lterm = d.w[5], ci = d.w[6], la = d.w[7];
   u64 A, B; u32 aux = 0;
-  if ((flags & ~plain) == 0u && (kind == RGB_MSG_AER_REPLY || kind == RGB_MSG_WRITTEN)) {
-    if ((d.w[2] | d.w[3] | d.w[4] | d.w[5]) != 0ull) return false;
-    A = d.w[6]; B = d.w[7];                                                         /* counted */
-  } else if ((flags & ~plain) == RGB_F_WROTE && kind == RGB_MSG_AER) {
-    const u64 fst = d.w[3], lst = d.w[4], la = d.w[7];
-    if ((d.w[2] | d.w[5]) != 0ull || fst > lst || lst - fst > 0xFFFFull || la > lst || lst - la > 0xFFFFull) return false;
-    A = lst; B = d.w[6];
+  if ((shape == 0u && kind < 32u && ((counted_kinds >> kind) & 1u)) ||
+      (kind == RGB_MSG_VOTE_RESULT && shape == (RGB_F_BECAME_LEADER | RGB_F_ROLE_CHANGED | RGB_F_LEADER_CHANGED))) {
+    if ((term | next | last | lterm) != 0ull) return false;
+    A = ci; B = la;                                                                 /* counted */
+  } else if (kind == RGB_MSG_HEARTBEAT_REPLY && shape == RGB_F_QUERY_QUORUM) {
+    if ((term | last | lterm) != 0ull || next > 0xFFFFFFFFull) return false;
+    A = ci; B = la; aux = (u32)next;                                                /* counted, with the query index */
+  } else if (stem == RGB_F_WROTE && aer) {
+    const u64 fst = next, lst = last;
+    if ((term | lterm) != 0ull || fst > lst || lst - fst > 0xFFFFull || la > lst || lst - la > 0xFFFFull) return false;
+    A = lst; B = ci;
     aux = (u32)(lst - fst) | ((u32)(lst - la) << 16);                               /* wrote */
-  } else if ((flags & ~plain) == (RGB_F_REPLY | RGB_F_REPLY_SUCCESS) && (kind == RGB_MSG_AER || kind == RGB_MSG_WRITTEN)) {
-    const u64 term = d.w[2], next = d.w[3], last = d.w[4], lterm = d.w[5], ci = d.w[6], la = d.w[7];
+  } else if (stem == (RGB_F_REPLY | RGB_F_REPLY_SUCCESS) && (aer || (kind == RGB_MSG_WRITTEN && stem == shape))) {
     if (next == 0ull) return false;
     A = next - 1ull; B = term;
-    const u64 d1 = A - last, d2 = term - lterm, d3 = ci + 512ull - A, d4 = A + 1ull - la;
-    if (last > A || d1 > 0xFFull || lterm > term || d2 > 0xFull || ci + 512ull < A || d3 > 0x3FFull || la > A + 1ull ||
+    const u64 d1 = A - last, d2 = term - lterm, d4 = next - la;
+    u32 d3;
+    if (last > A || d1 > 0xFFull || lterm > term || d2 > 0xFull || !biased_delta(ci, A, 512u, 0x3FFu, d3) || la > next ||
         d4 > 0x3FFull)
       return false;
-    aux = (u32)d1 | ((u32)d2 << 8) | ((u32)d3 << 12) | ((u32)d4 << 22);            /* confirmed */
+    aux = (u32)d1 | ((u32)d2 << 8) | (d3 << 12) | ((u32)d4 << 22);                 /* confirmed */
+  } else if (kind == RGB_MSG_HEARTBEAT_RPC && stem == (RGB_F_REPLY | RGB_F_REPLY_HEARTBEAT)) {
+    u32 dl;
+    if ((last | lterm) != 0ull || next > 0xFFFFull || !biased_delta(ci, la, 0x8000u, 0xFFFFu, dl)) return false;
+    A = ci; B = term;
+    aux = (u32)next | (dl << 16);                                                   /* answered */
+  } else if (kind == RGB_MSG_PRE_VOTE_RESULT && stem == RGB_F_SEND_VOTE_REQUESTS) {
+    if (next != 0ull || lterm > term || term - lterm > 0xFFull || ci > last || last - ci > 0xFFFull || la > last ||
+        last - la > 0xFFFull)
+      return false;
+    A = last; B = term;
+    aux = (u32)(term - lterm) | ((u32)(last - ci) << 8) | ((u32)(last - la) << 20); /* stood */
   } else {
     return false;
   }
@@ -4333,12 +4366,16 @@ __global__ __launch_bounds__(RGB_RES_BLOCK) void rgb_results_kernel(const ulongl
       const u32 aux = (u32)(a.y >> 32), f = flags & ~(u32)RGB_F_COMPACT;
       const u64 A = bb.x, B = bb.y;
       u64 w2 = 0, w3 = 0, w4 = 0, w5 = 0, ci, la;
-      if (f & RGB_F_REPLY) {
+      if (f & RGB_F_REPLY_HEARTBEAT) {                                            /* answered */
+        ci = A; w2 = B; w3 = (u64)(aux & 0xFFFFu); la = A + 32768ull - (u64)(aux >> 16);
+      } else if (f & RGB_F_REPLY) {                                               /* confirmed */
         w3 = A + 1ull; w2 = B; w4 = A - (u64)(aux & 0xFFu); w5 = B - (u64)((aux >> 8) & 0xFu);
         ci = A + (u64)((aux >> 12) & 0x3FFu) - 512ull; la = A + 1ull - (u64)((aux >> 22) & 0x3FFu);
       } else if (f & RGB_F_WROTE) {
         w4 = A; w3 = A - (u64)(aux & 0xFFFFu); ci = B; la = A - (u64)(aux >> 16);
-      } else { ci = A; la = B; }
+      } else if (f & RGB_F_SEND_VOTE_REQUESTS) {                                  /* stood */
+        w4 = A; w2 = B; w5 = B - (u64)(aux & 0xFFu); ci = A - (u64)((aux >> 8) & 0xFFFu); la = A - (u64)(aux >> 20);
+      } else { ci = A; la = B; w3 = (u64)aux; }                                   /* counted */
       a.y = (u64)f;
       bb = make_ulonglong2(w2, w3); c = make_ulonglong2(w4, w5); e = make_ulonglong2(ci, la);
     } else { c = src[2]; e = src[3]; }
