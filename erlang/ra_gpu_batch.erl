@@ -22,6 +22,7 @@
 -export([segment_info/4, segment_compact/6, segment_compact_group/4]).
 -export([segment_compact_plan/7, segment_compact_groups/7, major_compaction_batch/4]).
 -export([segment_flush/7, segment_flush_batch/5]).
+-export([wal_batch/6, wal_handle_batch/5]).
 -export([segment_read/5, segment_read_plan/3, segment_term_query_batch/2]).
 -export([crc32_spans/3, snapshot_build/3, snapshot_validate/3, snapshot_images/2, snapshot_recover_batch/2, accept_chunks/2]).
 -export([encode_msg/3, encode_msgs/1, decode_decision/1, decision_to_effects/3]).
@@ -519,6 +520,77 @@ wal_frame_batch(Ctx, Records, ComputeChecksums) ->
     Flags = case ComputeChecksums of true -> 0; false -> 1 end,
     {ok, Framed} = wal_frame(Ctx, RecsBin, iolist_to_binary(Data), Flags),
     Framed.
+
+%% WAL batch (src/ra_log_wal.erl:482-635, 800-812, 1050-1066): handle_batch/2 for a mailbox-ordered run of append
+%% commands in one call.  All records little endian.  CmdsBin = 64 bytes per command: writer:32 (slot in WritersBin),
+%% data_len:32, index:64, term:64, prev_index:64, smallest_index:64, tid:64, data_offset:64, 0:64.  WritersBin = 32
+%% bytes per slot: state:32 (0 undefined, 1 in_seq, 2 out_of_seq), id_ref:32 (16#FFFFFFFF: not in this file's
+%% writer-name cache), prev_index:64, uid_offset:64, uid_len:32, 0:32.  FileBin = file_size:64, entry_count:64,
+%% max_size:64, max_entries:64 (0 = undefined), next_id_ref:32, 0:32.  ResultsBin = 16 bytes per command:
+%% verdict:32 (low byte 0 not consumed, 1 write, 2 drop, 3 ignore, 4 resend; 16#100 Trunc, 16#200 long header),
+%% checksum:32, value:64 (write: offset in FramedBin; resend: the index to resend from).  EventsBin = 32 bytes per
+%% event: writer:32, range_first:32, term:64, tid:64, range_n:32, 0:32; RangesBin = first:64, last:64 per pair.
+%% TotalBin = status:32 (0 ok, 1 roll), n_consumed:32, n_written:32, n_events:32, n_ranges:32, next_id_ref:32,
+%% out_bytes:64, file_size:64, entry_count:64, 0:128.
+wal_batch(_Ctx, _CmdsBin, _WritersBin, _FileBin, _DataBin, _Flags) -> erlang:nif_error(not_loaded).
+
+%% Cmds = [{Slot, MtTid, ExpectedPrevIdx, Idx, Term, SmallestIdx, EntryBin}] in mailbox order, MtTid an integer the
+%% caller maps its ets tids to, ExpectedPrevIdx -1 passed as 0 (both compare the same with every P >= 0);
+%% Writers = [{State, IdRef, UId}] by slot, State = undefined | {in_seq, P} | {out_of_seq, P}, IdRef = the 22-bit
+%% number of the writer-name cache or undefined; File = {FileSize, EntryCount, MaxSize, MaxEntries | undefined, NextIdRef}.
+%% -> {Verdicts, FramedBin, Writers1, [{Slot, Term, MtTid, Seq}], File1, ok | {roll, NConsumed}}: Verdicts = one of
+%% write | drop | ignore | {resend, Idx} | not_consumed per command; FramedBin goes to file:write/2 as
+%% flush_pending/1's Pend; every {Slot, Term, MtTid, Seq} is a `written` event (Seq a ra_seq built from the pairs) and
+%% the input of update_ranges/5.  With {roll, N} the caller completes the batch, rolls the file and calls again with
+%% lists:nthtail(N, Cmds), Writers1 with every IdRef undefined, and the new file.  rollover, forget_writer and query
+%% messages, a UId whose Pid changes, counters, file I/O and sync stay in ra_log_wal.
+wal_handle_batch(Ctx, Cmds, Writers, {FileSize, EntryCount, MaxSize, MaxEntries0, NextIdRef}, ComputeChecksums) ->
+    MaxEntries = case MaxEntries0 of undefined -> 0; _ -> MaxEntries0 end,
+    {WritersBin, UIds, Off0} =
+        lists:foldl(fun({State, IdRef0, UId}, {W, D, Off}) ->
+                            {Kind, P} = case State of
+                                            undefined -> {0, 0};
+                                            {in_seq, P0} -> {1, P0};
+                                            {out_of_seq, P0} -> {2, P0}
+                                        end,
+                            IdRef = case IdRef0 of undefined -> 16#FFFFFFFF; _ -> IdRef0 end,
+                            Len = byte_size(UId),
+                            {<<W/binary, Kind:32/little, IdRef:32/little, P:64/little, Off:64/little, Len:32/little,
+                               0:32>>, [D, UId], Off + Len}
+                    end, {<<>>, [], 0}, Writers),
+    {CmdsBin, Data, _} =
+        lists:foldl(fun({Slot, Tid, Prev0, Idx, Term, Smallest, Bin}, {C, D, Off}) ->
+                            Len = byte_size(Bin),
+                            Prev = max(Prev0, 0),
+                            {<<C/binary, Slot:32/little, Len:32/little, Idx:64/little, Term:64/little, Prev:64/little,
+                               Smallest:64/little, Tid:64/little, Off:64/little, 0:64>>, [D, Bin], Off + Len}
+                    end, {<<>>, UIds, Off0}, Cmds),
+    FileBin = <<FileSize:64/little, EntryCount:64/little, MaxSize:64/little, MaxEntries:64/little,
+                NextIdRef:32/little, 0:32>>,
+    Flags = case ComputeChecksums of true -> 0; false -> 1 end,
+    {ok, {ResultsBin, WritersBin1}, Framed, {EventsBin, RangesBin}, TotalBin} =
+        wal_batch(Ctx, CmdsBin, WritersBin, FileBin, iolist_to_binary(Data), Flags),
+    <<Status:32/little, NConsumed:32/little, _NWritten:32/little, _NEvents:32/little, _NRanges:32/little,
+      NextIdRef1:32/little, _OutBytes:64/little, FileSize1:64/little, EntryCount1:64/little, _:128>> = TotalBin,
+    Verdicts = [case V band 16#FF of
+                    0 -> not_consumed; 1 -> write; 2 -> drop; 3 -> ignore; 4 -> {resend, Value}
+                end || <<V:32/little, _Sum:32, Value:64/little>> <= ResultsBin],
+    Writers1 = lists:zipwith(fun(<<Kind:32/little, IdRef:32/little, P:64/little, _:128>>, {_, _, UId}) ->
+                                     {case Kind of 0 -> undefined; 1 -> {in_seq, P}; 2 -> {out_of_seq, P} end,
+                                      case IdRef of 16#FFFFFFFF -> undefined; _ -> IdRef end, UId}
+                             end, [W || <<W:32/binary>> <= WritersBin1], Writers),
+    Pairs = list_to_tuple([{F, L} || <<F:64/little, L:64/little>> <= RangesBin]),
+    Events = [{Slot, Term, Tid,
+               lists:foldl(fun(K, Seq) ->
+                                   case element(K, Pairs) of
+                                       {I, I} -> [I | Seq];
+                                       {F, L} when L =:= F + 1 -> [L, F | Seq];
+                                       Range -> [Range | Seq]
+                                   end
+                           end, [], lists:seq(RF + 1, RF + RN))}
+              || <<Slot:32/little, RF:32/little, Term:64/little, Tid:64/little, RN:32/little, _:32>> <= EventsBin],
+    {Verdicts, Framed, Writers1, Events, {FileSize1, EntryCount1, MaxSize, MaxEntries0, NextIdRef1},
+     case Status of 0 -> ok; 1 -> {roll, NConsumed} end}.
 
 %% Recovery of one WAL file (src/ra_log_wal.erl:877-1033): the walk and every checksum in one
 %% call; returns the records to hand to recover_entry/5, in file order, or throws like the

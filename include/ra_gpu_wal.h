@@ -143,6 +143,139 @@ int rgb_wal_scan(const void *bytes, uint64_t n_bytes, rgb_wal_scanned *out, uint
 int rgb_wal_validate(rgb_ctx *ctx, const void *bytes, uint64_t n_bytes, const rgb_wal_scanned *recs,
                      uint32_t n, uint32_t *n_ok, uint32_t *status);
 
+/* ==== WAL batch: one mailbox-ordered batch of append commands in one call ========================
+ *
+ * ra_log_wal:handle_batch/2 for a batch of {append, ...} messages of any number of writers: the gap detection and
+ * smallest-live-index drop of handle_msg/2 (src/ra_log_wal.erl:551-586), serialize_header/3 with its writer-name
+ * cache (:482-499), the roll test (should_roll_wal/1, :1050-1066), the framed bytes of write_data/8 (:501-548) and the
+ * `written` events of incr_batch/8 and complete_batch_writer/3 (:596-635, :800-812).
+ *
+ * Per command, in mailbox order, with Trunc = (index == smallest_index) and the writer's state
+ * undefined | {in_seq, P} | {out_of_seq, P}; the clauses are tried in this order:
+ *   1. index < smallest_index                 DROP; the state becomes {in_seq, smallest_index - 1}
+ *   2. state {_, P}, prev_index =< P or Trunc  WRITE with Trunc
+ *   3. state undefined                         WRITE with Trunc = false
+ *   4. state {out_of_seq, _}                   IGNORE; the state stays
+ *   5. state {in_seq, P}                       RESEND, value = P + 1; the state becomes {out_of_seq, P}
+ * A WRITE first runs the roll test on the file as the commands before it left it: file_size > max_size, or
+ * max_entries != 0 and entry_count + 1 > max_entries.  The first WRITE command that finds it true is NOT consumed:
+ * status ROLL, n_consumed = its position, and verdicts, writer rows, bytes and events cover the commands before it.
+ * The caller writes the bytes, sends the events, rolls the file and calls again from that command with a fresh
+ * rgb_wal_file (and id_ref = RGB_WAL_NO_ID_REF in every writer row).  Otherwise the record is framed: 3 header bytes
+ * <<Trunc:1, 1:1, IdRef:22>> for a writer that has an id_ref, else <<Trunc:1, 0:1, Next:22, IdDataLen:16, UId/binary>>
+ * with id_ref = next_id_ref, which rises by one (mailbox order of first appearance); then
+ * <<Checksum:32, EntryDataLen:32, Idx:64, Term:64>> and the payload.  The state becomes {in_seq, index}, entry_count
+ * rises by one, and file_size by the reference's DataSize -- which counts a HeaderLen of 2 for the 3 bytes of a known
+ * writer with Trunc set (:484-485): the roll test and the returned file_size use that accounted size, offsets into
+ * `out` the real one.
+ *
+ * Events: per writer the consumed WRITE commands fall into runs of consecutive commands with equal (term, tid); each
+ * run is one event, oldest first.  Its indexes are those of its commands that are smaller than every later index of
+ * the run (ra_seq:append(Idx, ra_seq:limit(Idx - 1, Seq))), not below the smallest_index of the run's LAST command
+ * (ra_seq:floor/2): never empty.  Event rows are sorted by (writer, run order); an event owns range_n ascending, not
+ * adjacent (first, last) pairs of uint64_t from pair range_first of the pair list -- the form rgb_submit_seq takes.
+ *
+ * `cmds` and `writers` are HOST arrays in both forms: validated on the host and staged by the library, which also
+ * orders the commands by writer (one counting pass).  RGB_E_INVAL, nothing enqueued and nothing written: a writer slot
+ * >= n_writers, a payload or uid outside the data buffer, uid_len > 65535, an unknown state, id_ref >= 2^22 (other than
+ * RGB_WAL_NO_ID_REF), next_id_ref + the writers without an id_ref > 2^22, unknown flags, NULLs.  n == 0 is legal.
+ * rollover, forget_writer and query messages, a UId whose Pid changes (a slot is one {UId, Pid}), update_ranges/5,
+ * roll_over/1, counters, file I/O and sync stay with the caller, which splits its batch there.
+ *
+ * SPACE: out_bytes, events_cap or ranges_cap is too small; the total says what is needed.  `out` is not touched; the
+ * command rows (checksums included), the writer rows and the total are written as they would be; the event rows and
+ * the pair list are written whenever both fit their caps.
+ *
+ * Seven launches whatever n and n_writers are.  The scratch lives in the context (released by rgb_close): one batch
+ * call per context at a time.  Only a payload's and a uid's own bytes are read, only the records' own bytes written. */
+typedef struct rgb_wal_cmd {         /* 64 bytes */
+  uint32_t writer;                   /* slot in `writers` */
+  uint32_t data_len;
+  uint64_t index, term;
+  uint64_t prev_index;               /* ExpectedPrevIdx; -1 (index 0) is passed as 0: the same against every P >= 0 */
+  uint64_t smallest_index;           /* smallest_live_index/2 as read for THIS message (:554) */
+  uint64_t tid;                      /* MtTid, an opaque value compared for equality */
+  uint64_t data_offset;              /* payload = data[data_offset .. + data_len) */
+  uint64_t _pad;
+} rgb_wal_cmd;
+
+#define RGB_WAL_W_UNDEFINED  0u
+#define RGB_WAL_W_IN_SEQ     1u
+#define RGB_WAL_W_OUT_OF_SEQ 2u
+#define RGB_WAL_NO_ID_REF    0xFFFFFFFFu   /* the writer is not in this file's writer-name cache */
+#define RGB_WAL_MAX_ID_REFS  (1u << 22)
+
+typedef struct rgb_wal_writer {      /* 32 bytes, in and out */
+  uint32_t state;                    /* RGB_WAL_W_* */
+  uint32_t id_ref;                   /* or RGB_WAL_NO_ID_REF */
+  uint64_t prev_index;               /* P; ignored with RGB_WAL_W_UNDEFINED */
+  uint64_t uid_offset;               /* UId = data[uid_offset .. + uid_len) */
+  uint32_t uid_len, _pad;
+} rgb_wal_writer;
+
+typedef struct rgb_wal_file {        /* 40 bytes; the total returns the fields that change */
+  uint64_t file_size, entry_count;
+  uint64_t max_size, max_entries;    /* max_entries 0 = undefined */
+  uint32_t next_id_ref, _pad;
+} rgb_wal_file;
+
+#define RGB_WAL_V_NOT_CONSUMED 0u
+#define RGB_WAL_V_WRITE        1u
+#define RGB_WAL_V_DROP         2u
+#define RGB_WAL_V_IGNORE       3u
+#define RGB_WAL_V_RESEND       4u
+#define RGB_WAL_V_MASK         0xFFu
+#define RGB_WAL_V_TRUNC        0x100u  /* WRITE: the record's Trunc bit */
+#define RGB_WAL_V_FIRST        0x200u  /* WRITE: the long header (first appearance in this file) */
+
+typedef struct rgb_wal_cmd_result {  /* 16 bytes, one per command */
+  uint32_t verdict;                  /* RGB_WAL_V_* | flags */
+  uint32_t checksum;                 /* WRITE: the record's Checksum (0 with RGB_WAL_NO_CHECKSUMS) */
+  uint64_t value;                    /* WRITE: the record's offset in `out`; RESEND: P + 1; otherwise 0 */
+} rgb_wal_cmd_result;
+
+typedef struct rgb_wal_event {       /* 32 bytes: {written, Term, Seq} to one writer, with the run's MtTid */
+  uint32_t writer, range_first;
+  uint64_t term, tid;
+  uint32_t range_n, _pad;
+} rgb_wal_event;
+
+#define RGB_WAL_BATCH_OK    0u
+#define RGB_WAL_BATCH_ROLL  1u       /* command n_consumed found the roll test true */
+#define RGB_WAL_BATCH_SPACE 2u       /* wins over ROLL; n_consumed still says where the call would have ended */
+
+typedef struct rgb_wal_batch_total { /* 64 bytes */
+  uint32_t status, n_consumed;
+  uint32_t n_written, n_events;
+  uint32_t n_ranges, next_id_ref;
+  uint64_t out_bytes;                /* OK, ROLL: bytes of `out` written; SPACE: bytes needed */
+  uint64_t file_size, entry_count;   /* of the file behind the consumed commands (accounted size) */
+  uint64_t _pad[2];
+} rgb_wal_batch_total;
+
+/* Host helper, pure: the validation of the calls below, and sizes that always suffice: *out_bound = the payload bytes
+ * + 27 * n + the sum of 2 + uid_len over the writers, *events_bound = *ranges_bound = n. */
+int rgb_wal_batch_bound(const rgb_wal_cmd *cmds, uint32_t n, const rgb_wal_writer *writers, uint32_t n_writers,
+                        const rgb_wal_file *file, uint64_t data_bytes, uint64_t *out_bound, uint32_t *events_bound,
+                        uint32_t *ranges_bound);
+
+/* d_results: n rgb_wal_cmd_result rows, d_writers_out: n_writers rgb_wal_writer rows, d_events: events_cap
+ * rgb_wal_event rows, d_ranges: 2 * ranges_cap uint64_t, *d_total: one rgb_wal_batch_total -- all in device memory,
+ * 8-byte aligned; d_data and d_out may have any alignment.  flags: RGB_WAL_NO_CHECKSUMS.  Enqueued on `stream`
+ * (NULL = the context's stream), no synchronisation. */
+int rgb_wal_batch_device(rgb_ctx *ctx, const rgb_wal_cmd *cmds, uint32_t n, const rgb_wal_writer *writers,
+                         uint32_t n_writers, const rgb_wal_file *file, const void *d_data, uint64_t data_bytes,
+                         uint32_t flags, void *d_results, void *d_writers_out, void *d_out, uint64_t out_bytes,
+                         void *d_events, uint32_t events_cap, void *d_ranges, uint32_t ranges_cap, void *d_total,
+                         void *stream);
+/* Host-buffer form: synchronises.  `out` (its first out_bytes bytes) is written with the status OK or ROLL only;
+ * events and ranges (their first n_events rows / n_ranges pairs) whenever both fit. */
+int rgb_wal_batch(rgb_ctx *ctx, const rgb_wal_cmd *cmds, uint32_t n, const rgb_wal_writer *writers, uint32_t n_writers,
+                  const rgb_wal_file *file, const void *data, uint64_t data_bytes, uint32_t flags,
+                  rgb_wal_cmd_result *results, rgb_wal_writer *writers_out, void *out, uint64_t out_bytes,
+                  rgb_wal_event *events, uint32_t events_cap, uint64_t *ranges, uint32_t ranges_cap,
+                  rgb_wal_batch_total *total);
+
 /* ==== segments and snapshots: batched CRC-32 ===============================================
  *
  * Everything Ra writes behind the WAL is checksummed with erlang:crc32 -- zlib's CRC-32 (reflected

@@ -158,6 +158,26 @@ WAL_REC_FIRST, WAL_REC_VALIDATE, WAL_REC_UNKNOWN = 1, 2, 4
 WAL_END_ZEROS, WAL_END_DATA, WAL_END_CAP = 0, 1, 2
 WAL_CLEAN, WAL_DROPPED_LAST, WAL_CORRUPT = 0, 1, 2
 WAL_FILE_HEADER = b"RAWA\x01"
+# WAL batch (same header): a command, a writer slot, the file, a command's result, a written event, the total
+WAL_CMD_DTYPE = np.dtype([("writer", u32), ("data_len", u32), ("index", u64), ("term", u64), ("prev_index", u64),
+                          ("smallest_index", u64), ("tid", u64), ("data_offset", u64), ("_pad", u64)])
+WAL_WRITER_DTYPE = np.dtype([("state", u32), ("id_ref", u32), ("prev_index", u64), ("uid_offset", u64),
+                             ("uid_len", u32), ("_pad", u32)])
+WAL_FILE_DTYPE = np.dtype([("file_size", u64), ("entry_count", u64), ("max_size", u64), ("max_entries", u64),
+                           ("next_id_ref", u32), ("_pad", u32)])
+WAL_CMD_RESULT_DTYPE = np.dtype([("verdict", u32), ("checksum", u32), ("value", u64)])
+WAL_EVENT_DTYPE = np.dtype([("writer", u32), ("range_first", u32), ("term", u64), ("tid", u64), ("range_n", u32),
+                            ("_pad", u32)])
+WAL_BATCH_TOTAL_DTYPE = np.dtype([("status", u32), ("n_consumed", u32), ("n_written", u32), ("n_events", u32),
+                                  ("n_ranges", u32), ("next_id_ref", u32), ("out_bytes", u64), ("file_size", u64),
+                                  ("entry_count", u64), ("_pad", u64, (2,))])
+assert (WAL_CMD_DTYPE.itemsize, WAL_WRITER_DTYPE.itemsize, WAL_FILE_DTYPE.itemsize, WAL_CMD_RESULT_DTYPE.itemsize,
+        WAL_EVENT_DTYPE.itemsize, WAL_BATCH_TOTAL_DTYPE.itemsize) == (64, 32, 40, 16, 32, 64)
+WAL_W_UNDEFINED, WAL_W_IN_SEQ, WAL_W_OUT_OF_SEQ = range(3)
+WAL_NO_ID_REF, WAL_MAX_ID_REFS = 0xFFFFFFFF, 1 << 22
+WAL_V_NOT_CONSUMED, WAL_V_WRITE, WAL_V_DROP, WAL_V_IGNORE, WAL_V_RESEND = range(5)
+WAL_V_MASK, WAL_V_TRUNC, WAL_V_FIRST = 0xFF, 0x100, 0x200
+WAL_BATCH_OK, WAL_BATCH_ROLL, WAL_BATCH_SPACE = range(3)
 # segments and snapshots (same header)
 SEG_ENTRY_DTYPE = np.dtype([("index", u64), ("term", u64), ("data_offset", u64), ("data_len", u32), ("crc", u32)])
 assert SEG_ENTRY_DTYPE.itemsize == 32

@@ -981,6 +981,55 @@ static ERL_NIF_TERM nif_segment_flush(ErlNifEnv *env, int argc, const ERL_NIF_TE
   return enif_make_tuple3(env, enif_make_atom(env, "ok"), enif_make_binary(env, &pieces), enif_make_binary(env, &out));
 }
 
+/* wal_batch(Ctx, CmdsBin, WritersBin, FileBin, DataBin, Flags) -> {ok, {ResultsBin, WritersBin1}, FramedBin,
+ * {EventsBin, RangesBin}, TotalBin} | {error, _}: ra_log_wal:handle_batch/2 for a mailbox-ordered batch of append
+ * commands (src/ra_log_wal.erl:482-635, 800-812, 1050-1066).  CmdsBin = n rgb_wal_cmd records, WritersBin = W
+ * rgb_wal_writer records, FileBin = one rgb_wal_file, DataBin = the packed payloads and uids; ResultsBin = one
+ * rgb_wal_cmd_result per command, WritersBin1 = the writers afterwards, FramedBin = the bytes flush_pending/1 writes,
+ * EventsBin = rgb_wal_event records whose ranges are (first, last) pairs of native 64-bit integers in RangesBin,
+ * TotalBin = one rgb_wal_batch_total (status 1: the file must roll before command n_consumed).  Flags: 1 =
+ * compute_checksums false. */
+static ERL_NIF_TERM nif_wal_batch(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  nif_ctx *c; ErlNifBinary cm, w, f, d, res, wout, out, ev, rg, tot; unsigned flags; uint64_t bound = 0; uint32_t evb = 0, rgb = 0;
+  (void)argc;
+  if (!get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &cm) || !enif_inspect_binary(env, argv[2], &w) ||
+      !enif_inspect_binary(env, argv[3], &f) || !enif_inspect_binary(env, argv[4], &d) ||
+      !enif_get_uint(env, argv[5], &flags) || cm.size % sizeof(rgb_wal_cmd) != 0 || w.size % sizeof(rgb_wal_writer) != 0 ||
+      f.size != sizeof(rgb_wal_file) || cm.size / sizeof(rgb_wal_cmd) > 0xFFFFFFFFu ||
+      w.size / sizeof(rgb_wal_writer) > 0xFFFFFFFFu)
+    return enif_make_badarg(env);
+  const uint32_t n = (uint32_t)(cm.size / sizeof(rgb_wal_cmd)), n_w = (uint32_t)(w.size / sizeof(rgb_wal_writer));
+  const rgb_wal_cmd *cmds = (const rgb_wal_cmd *)cm.data;
+  const rgb_wal_writer *writers = (const rgb_wal_writer *)w.data;
+  const rgb_wal_file *file = (const rgb_wal_file *)f.data;
+  int rc = rgb_wal_batch_bound(cmds, n, writers, n_w, file, d.size, &bound, &evb, &rgb);
+  if (rc) return mk_error(env, c, rc);
+  ErlNifBinary *all[] = {&res, &wout, &out, &ev, &rg, &tot};
+  const size_t sizes[] = {(size_t)n * sizeof(rgb_wal_cmd_result), (size_t)n_w * sizeof(rgb_wal_writer), (size_t)bound,
+                          (size_t)evb * sizeof(rgb_wal_event), (size_t)rgb * 16u, sizeof(rgb_wal_batch_total)};
+  for (int i = 0; i < 6; ++i)
+    if (!enif_alloc_binary(sizes[i] ? sizes[i] : 1, all[i])) {
+      while (i--) enif_release_binary(all[i]);
+      return mk_error(env, c, RGB_E_NOMEM);
+    }
+  rgb_wal_batch_total *t = (rgb_wal_batch_total *)tot.data;
+  rc = rgb_wal_batch(c->ctx, cmds, n, writers, n_w, file, d.data, d.size, flags, (rgb_wal_cmd_result *)res.data,
+                     (rgb_wal_writer *)wout.data, out.data, bound, (rgb_wal_event *)ev.data, evb, (uint64_t *)rg.data, rgb, t);
+  if (rc || t->status == RGB_WAL_BATCH_SPACE) {          /* (the bounds always suffice: no SPACE from here) */
+    for (int i = 0; i < 6; ++i) enif_release_binary(all[i]);
+    return mk_error(env, c, rc ? rc : RGB_E_INVAL);
+  }
+  enif_realloc_binary(&res, sizes[0]);
+  enif_realloc_binary(&wout, sizes[1]);
+  enif_realloc_binary(&out, (size_t)t->out_bytes);
+  enif_realloc_binary(&ev, (size_t)t->n_events * sizeof(rgb_wal_event));
+  enif_realloc_binary(&rg, (size_t)t->n_ranges * 16u);
+  ERL_NIF_TERM rows = enif_make_tuple2(env, enif_make_binary(env, &res), enif_make_binary(env, &wout));
+  ERL_NIF_TERM events = enif_make_tuple2(env, enif_make_binary(env, &ev), enif_make_binary(env, &rg));
+  return enif_make_tuple5(env, enif_make_atom(env, "ok"), rows, enif_make_binary(env, &out), events,
+                          enif_make_binary(env, &tot));
+}
+
 /* segment_read(Ctx, SourcesBin, FilesBin, ReqBin, Flags) -> {ok, RowsBin, ResultsBin, OutBin} | {error, _}: a read plan
  * over many segment files in one call -- ra_log_segment:read_sparse/4, fold/6 and term_query/2 (src/ra_log_segment.erl:
  * 340-359, 375-598, 652-689) as ra_log_segments:exec_read_plan/6 drives them (src/ra_log_segments.erl:398-622).
@@ -1123,6 +1172,7 @@ static ErlNifFunc nif_funcs[] = {
   {"segment_compact_groups", 7, nif_segment_compact_groups, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_flush", 7, nif_segment_flush, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"segment_read", 5, nif_segment_read, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"wal_batch", 6, nif_wal_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"crc32_spans", 3, nif_crc32_spans, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"snapshot_build", 3, nif_snapshot_build, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"snapshot_validate", 3, nif_snapshot_validate, ERL_NIF_DIRTY_JOB_IO_BOUND},

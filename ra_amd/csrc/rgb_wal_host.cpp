@@ -86,6 +86,62 @@ extern "C" int rgb_wal_scan(const void *bytes, uint64_t n_bytes, rgb_wal_scanned
 }
 
 
+/* ---- WAL batch: validation, the stable per-writer order of the commands, the bound ---------------------- */
+
+/* The validation of every rgb_wal_batch call, and in the same pass what the device kernels take as staged input:
+ * wstart[w] (n_writers + 1 values) = the commands of the writers in front of w, order[wstart[w] ..) = the positions of
+ * w's commands, ascending.  order / wstart may be NULL (both): validation and sums only.  *payload_bytes = the sum of
+ * data_len, *header_bytes = the sum of 2 + uid_len over the writers, *longest = the most commands of one writer. */
+extern "C" int rgb_wal_batch_check(const rgb_wal_cmd *cmds, uint32_t n, const rgb_wal_writer *writers, uint32_t n_writers,
+                                   const rgb_wal_file *file, uint64_t data_bytes, uint32_t flags, uint32_t *order,
+                                   uint32_t *wstart, uint64_t *payload_bytes, uint64_t *header_bytes, uint32_t *longest) {
+  if (!file || (n && !cmds) || (n_writers && !writers) || (flags & ~RGB_WAL_NO_CHECKSUMS)) return RGB_E_INVAL;
+  if ((order == nullptr) != (wstart == nullptr)) return RGB_E_INVAL;
+  auto slice_ok = [&](uint64_t off, uint64_t len) { return off <= data_bytes && len <= data_bytes - off; };
+  uint64_t unnamed = 0, hdr = 0, pay = 0;
+  for (uint32_t w = 0; w < n_writers; ++w) {
+    const rgb_wal_writer &wr = writers[w];
+    if (wr.state > RGB_WAL_W_OUT_OF_SEQ || wr.uid_len > 65535u || !slice_ok(wr.uid_offset, wr.uid_len)) return RGB_E_INVAL;
+    if (wr.id_ref == RGB_WAL_NO_ID_REF) unnamed += 1;
+    else if (wr.id_ref >= RGB_WAL_MAX_ID_REFS) return RGB_E_INVAL;
+    hdr += 2u + wr.uid_len;
+  }
+  if (file->next_id_ref > RGB_WAL_MAX_ID_REFS || unnamed > RGB_WAL_MAX_ID_REFS - file->next_id_ref) return RGB_E_INVAL;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (cmds[i].writer >= n_writers || !slice_ok(cmds[i].data_offset, cmds[i].data_len)) return RGB_E_INVAL;
+    pay += cmds[i].data_len;
+  }
+  uint32_t most = 0;
+  if (wstart) {                                         /* counting sort by writer: stable, so mailbox order within one */
+    for (uint32_t w = 0; w <= n_writers; ++w) wstart[w] = 0;
+    for (uint32_t i = 0; i < n; ++i) wstart[cmds[i].writer + 1u] += 1u;
+    for (uint32_t w = 0; w < n_writers; ++w) {
+      most = wstart[w + 1u] > most ? wstart[w + 1u] : most;
+      wstart[w + 1u] += wstart[w];
+    }
+    for (uint32_t i = 0; i < n; ++i) order[wstart[cmds[i].writer]++] = i;   /* wstart[w] is now the END of w ... */
+    for (uint32_t w = n_writers; w > 0; --w) wstart[w] = wstart[w - 1u];       /* ... which is the start of w + 1 */
+    wstart[0] = 0;
+  }
+  if (payload_bytes) *payload_bytes = pay;
+  if (header_bytes) *header_bytes = hdr;
+  if (longest) *longest = most;
+  return RGB_OK;
+}
+
+extern "C" int rgb_wal_batch_bound(const rgb_wal_cmd *cmds, uint32_t n, const rgb_wal_writer *writers, uint32_t n_writers,
+                                   const rgb_wal_file *file, uint64_t data_bytes, uint64_t *out_bound,
+                                   uint32_t *events_bound, uint32_t *ranges_bound) {
+  if (!out_bound || !events_bound || !ranges_bound) return RGB_E_INVAL;
+  uint64_t pay = 0, hdr = 0;
+  const int rc = rgb_wal_batch_check(cmds, n, writers, n_writers, file, data_bytes, 0u, nullptr, nullptr, &pay, &hdr, nullptr);
+  if (rc) return rc;
+  *out_bound = pay + 27ull * n + hdr;                   /* 3 + 24 per record, and 2 + uid_len more for each long header */
+  *events_bound = n;
+  *ranges_bound = n;
+  return RGB_OK;
+}
+
 /* the emulated library (tests/native) builds the WAL sources as one unit: the segment part rides along */
 #ifdef RGB_HOST_EMULATION
 #include "rgb_segment.hip"

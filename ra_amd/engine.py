@@ -45,6 +45,7 @@ OPTIONAL_IN_OLD_BUILDS = {"rgb_synth_tick_stamped_device", "rgb_synth_stamps_res
                           "rgb_submit_commit", "rgb_submit_raw"} | set(COMM_EXPORTS)
 WAL_EXPORTS = ["rgb_wal_adler32_device", "rgb_wal_adler32", "rgb_wal_layout", "rgb_wal_frame_device",
                "rgb_wal_frame", "rgb_wal_scan", "rgb_wal_validate",
+               "rgb_wal_batch_bound", "rgb_wal_batch_device", "rgb_wal_batch",
                "rgb_crc32_device", "rgb_crc32", "rgb_crc32_stream_device", "rgb_crc32_stream", "rgb_segment_layout",
                "rgb_segment_build_device", "rgb_segment_build", "rgb_segment_scan", "rgb_segment_validate",
                "rgb_segment_compact_bound", "rgb_segment_info_device", "rgb_segment_info", "rgb_segment_compact_device",
@@ -226,6 +227,11 @@ def lib():
                                                     C.c_uint64, vp, vp]
     L.rgb_segment_compact_groups.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, vp, u32, C.c_uint64, u32, vp,
                                              C.c_uint64, vp]
+    L.rgb_wal_batch_bound.argtypes = [vp, u32, vp, u32, vp, C.c_uint64, u64p, u32p, u32p]
+    L.rgb_wal_batch_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.c_uint64, u32, vp, vp, vp, C.c_uint64, vp, u32,
+                                       vp, u32, vp, vp]
+    L.rgb_wal_batch.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.c_uint64, u32, vp, vp, vp, C.c_uint64, vp, u32, vp, u32,
+                                vp]
     L.rgb_segment_flush_bound.argtypes = [vp, u32, u32, C.c_uint64, u64p, u32p]
     L.rgb_segment_flush_device.argtypes = [vp, vp, u32, vp, u32, vp, C.c_uint64, u32, C.c_uint64, u32, vp, u32, vp,
                                            C.c_uint64, vp, vp]
@@ -608,6 +614,59 @@ class RaGpuBatch:
                                              scanned.ctypes.data if len(scanned) else None, len(scanned),
                                              C.byref(n_ok), C.byref(status)), "rgb_wal_validate")
         return n_ok.value, status.value
+
+    # -- WAL batch: a mailbox-ordered batch of append commands in one call (include/ra_gpu_wal.h) --
+    def wal_batch_device(self, cmds: np.ndarray, writers: np.ndarray, file: np.ndarray, d_data: int, data_bytes: int,
+                         d_results: int, d_writers_out: int, d_out: int, out_bytes: int, d_events: int, events_cap: int,
+                         d_ranges: int, ranges_cap: int, d_total: int, flags: int = 0, stream: int = 0):
+        """ra_log_wal:handle_batch/2 for a batch of append commands (src/ra_log_wal.erl:482-635, 800-812, 1050-1066):
+        abi.WAL_CMD_RESULT_DTYPE rows, the new abi.WAL_WRITER_DTYPE rows, the framed bytes, abi.WAL_EVENT_DTYPE rows
+        with their (first, last) pairs and one abi.WAL_BATCH_TOTAL_DTYPE record, all into device memory.  `cmds`,
+        `writers` and `file` are host arrays; enqueues and returns."""
+        cmds = np.ascontiguousarray(cmds, dtype=abi.WAL_CMD_DTYPE)
+        writers = np.ascontiguousarray(writers, dtype=abi.WAL_WRITER_DTYPE)
+        file = np.ascontiguousarray(file, dtype=abi.WAL_FILE_DTYPE).reshape(1)
+        self._check(self._L.rgb_wal_batch_device(self._h, cmds.ctypes.data if len(cmds) else None, len(cmds),
+                                                 writers.ctypes.data if len(writers) else None, len(writers),
+                                                 file.ctypes.data, d_data or None, data_bytes, flags, d_results or None,
+                                                 d_writers_out or None, d_out or None, out_bytes, d_events or None,
+                                                 events_cap, d_ranges or None, ranges_cap, d_total or None,
+                                                 stream or None), "rgb_wal_batch_device")
+
+    def wal_batch(self, cmds: np.ndarray, writers: np.ndarray, file: np.ndarray, data: np.ndarray, flags: int = 0,
+                  out_bytes: int | None = None, events_cap: int | None = None, ranges_cap: int | None = None):
+        """Host-buffer form: (total record, result rows, writer rows, out bytes, event rows, pairs as an (n_ranges, 2)
+        array).  The buffers default to wal_batch_bound's sizes.  With abi.WAL_BATCH_SPACE the out bytes are None,
+        and events and pairs are None unless both fit their caps."""
+        cmds = np.ascontiguousarray(cmds, dtype=abi.WAL_CMD_DTYPE)
+        writers = np.ascontiguousarray(writers, dtype=abi.WAL_WRITER_DTYPE)
+        file = np.ascontiguousarray(file, dtype=abi.WAL_FILE_DTYPE).reshape(1)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if out_bytes is None or events_cap is None or ranges_cap is None:
+            ob, eb, rb = wal_batch_bound(cmds, writers, file, len(data))
+            out_bytes = ob if out_bytes is None else out_bytes
+            events_cap = eb if events_cap is None else events_cap
+            ranges_cap = rb if ranges_cap is None else ranges_cap
+        results = np.zeros(len(cmds), dtype=abi.WAL_CMD_RESULT_DTYPE)
+        writers_out = np.zeros(len(writers), dtype=abi.WAL_WRITER_DTYPE)
+        out = np.zeros(out_bytes, dtype=np.uint8)
+        events = np.zeros(events_cap, dtype=abi.WAL_EVENT_DTYPE)
+        ranges = np.zeros((ranges_cap, 2), dtype=np.uint64)
+        total = np.zeros(1, dtype=abi.WAL_BATCH_TOTAL_DTYPE)
+        self._check(self._L.rgb_wal_batch(self._h, cmds.ctypes.data if len(cmds) else None, len(cmds),
+                                          writers.ctypes.data if len(writers) else None, len(writers), file.ctypes.data,
+                                          data.ctypes.data if len(data) else None, len(data), flags,
+                                          results.ctypes.data if len(cmds) else None,
+                                          writers_out.ctypes.data if len(writers) else None,
+                                          out.ctypes.data if out_bytes else None, out_bytes,
+                                          events.ctypes.data if events_cap else None, events_cap,
+                                          ranges.ctypes.data if ranges_cap else None, ranges_cap, total.ctypes.data),
+                    "rgb_wal_batch")
+        t = total[0]
+        fit = int(t["n_events"]) <= events_cap and int(t["n_ranges"]) <= ranges_cap
+        space = int(t["status"]) == abi.WAL_BATCH_SPACE
+        return (t, results, writers_out, None if space else out[:int(t["out_bytes"])],
+                events[:int(t["n_events"])] if fit else None, ranges[:int(t["n_ranges"])] if fit else None)
 
     # -- segments and snapshots: batched CRC-32 (include/ra_gpu_wal.h) ------------------
     def crc32_device(self, d_entries: int, n: int, d_data: int, data_bytes: int, d_crcs: int, stream: int = 0):
@@ -1101,6 +1160,21 @@ def wal_layout(records: np.ndarray, base: int = 0) -> int:
     """Fill out_offset for back-to-back records from `base`; returns the end offset (host helper)."""
     assert records.dtype == abi.WAL_RECORD_DTYPE and records.flags["C_CONTIGUOUS"]
     return int(lib().rgb_wal_layout(records.ctypes.data if len(records) else None, len(records), base))
+
+
+def wal_batch_bound(cmds, writers, file, data_bytes: int):
+    """(bytes of `out`, event rows, pairs) that always suffice for a WAL batch call -- host helper, no device work;
+    RgbError(RGB_E_INVAL) for what the batch calls refuse."""
+    cmds = np.ascontiguousarray(cmds, dtype=abi.WAL_CMD_DTYPE)
+    writers = np.ascontiguousarray(writers, dtype=abi.WAL_WRITER_DTYPE)
+    file = np.ascontiguousarray(file, dtype=abi.WAL_FILE_DTYPE).reshape(1)
+    out, ev, rg = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+    rc = lib().rgb_wal_batch_bound(cmds.ctypes.data if len(cmds) else None, len(cmds),
+                                   writers.ctypes.data if len(writers) else None, len(writers), file.ctypes.data,
+                                   data_bytes, C.byref(out), C.byref(ev), C.byref(rg))
+    if rc != 0:
+        raise RgbError(rc, "rgb_wal_batch_bound")
+    return out.value, ev.value, rg.value
 
 
 def wal_scan(file_bytes, cap: int | None = None):
